@@ -1,7 +1,7 @@
 """Throughput benchmark: the flagship training step on N GPUs of one node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model cnn|linear]
-                    [--scaling weak|strong|both]
+                    [--scaling weak|strong|both] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,20 @@ fc 128->10, log-softmax/NLL) trained with DDP (bucketed all-reduce over xGMI) an
 SGD-momentum, bf16 compute / fp32 master weights, on synthetic 1x28x28 data of MNIST
 size (60k) with random-init weights.
 
-Two scaling modes (both measured by default, one JSON line):
+Two scaling modes (one JSON line):
   weak   -- 256 images per rank (global batch 256 N): the headline `value`;
   strong -- the reference's own DDP semantics: the node batch 256 is split over the
             ranks (multi_proc_single_gpu.py:174, --batch-size 256 -> 128/64/32 per rank
             at N = 2/4/8), reported under "strong" (at N = 1 the two coincide).
+A plain run measures only what the headline needs, the weak mode; --full measures both
+(as does --scaling both).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path left with its
+last step to DIR/<name>.npy: params (fp32 master weights), one array per optimizer state
+buffer (momentum_buffer, or exp_avg / exp_avg_sq) and train_metrics (the fp64 device
+accumulators [loss sum, correct, count]).  Weights, data and sampler orders are seeded and
+the window's place in the epoch follows from the arguments, so two runs with the same
+arguments train on the same inputs.
 
 A timed step is the complete training step: batch gather + normalise, forward, loss,
 backward, gradient all-reduce, optimizer update.  The timed window is placed so that an
@@ -54,7 +63,14 @@ def parse(argv=None):
     ap.add_argument("--model", choices=["cnn", "linear"], default="cnn")
     ap.add_argument("--batch-per-rank", type=int, default=NODE_BATCH,
                     help="per-rank batch of the weak-scaling measurement")
-    ap.add_argument("--scaling", choices=["weak", "strong", "both"], default="both")
+    ap.add_argument("--scaling", choices=["weak", "strong", "both"], default=None,
+                    help="default: weak (the headline); both with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the strong-scaling "
+                         "configuration (reported under \"strong\")")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step left (weights, optimizer "
+                         "state, train metrics) to DIR/<name>.npy")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default=None,
                     help="CNN compute dtype (default bf16; fp32 = the reference's precision on the "
                          "fp32 MFMA); the Linear model always runs fp32")
@@ -68,7 +84,19 @@ def parse(argv=None):
                     help="launch + rendezvous only (gloo, CPU): each rank joins the process "
                          "group, all-reduces its rank and rank 0 prints one JSON line; tests the "
                          "self-spawn path without a GPU")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.scaling is None:
+        a.scaling = "both" if a.full else "weak"
+    return a
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """Write each tensor as path/<name>.npy in its own dtype (fp32 weights and optimizer
+    state, fp64 metrics: 9.6 MB for the CNN with SGD momentum)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().cpu().numpy())
 
 
 RCCL_MODES = ("carry", "nocarry", "side", "early", "zero")
@@ -358,8 +386,9 @@ def main():
             x = float(t.item())
         return x
 
-    def measure(B: int) -> dict:
-        """Calibrate the transport for per-rank batch B, then time a.steps steps."""
+    def measure(B: int, dump: bool = False) -> dict:
+        """Calibrate the transport for per-rank batch B, then time a.steps steps (dump: this
+        is the measurement --dump-outputs records)."""
         prog = TrainProgram(model, dtype, arena, opt, first, train, test, B, use_graphs=a.graphs)
         # the reference's epoch (DataLoader drop_last=False, S:152-157): the rank's padded
         # DistributedSampler share in full batches, then one ragged tail batch
@@ -592,6 +621,9 @@ def main():
         prog.sync_master()
         if not torch.isfinite(arena.params).all():
             raise RuntimeError("non-finite parameters after the benchmark")
+        if dump and a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"params": arena.params, **opt.state_buffers(),
+                                          "train_metrics": prog.metrics.train_view()})
         if ws > 1:
             # DDP keeps identical replicas: every rank must hold the same weights and
             # optimizer state bit for bit after the timed window
@@ -616,12 +648,12 @@ def main():
     strong_B = max(1, NODE_BATCH // ws)
     res = {}
     if a.scaling in ("weak", "both"):
-        res["weak"] = measure(a.batch_per_rank)
+        res["weak"] = measure(a.batch_per_rank, dump=True)
     if a.scaling in ("strong", "both"):
         if "weak" in res and strong_B == a.batch_per_rank:
             res["strong"] = res["weak"]
         else:
-            res["strong"] = measure(strong_B)
+            res["strong"] = measure(strong_B, dump="weak" not in res)
     main_mode = "weak" if "weak" in res else "strong"
     m = res[main_mode]
 

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_contract(gpu):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20",
-                        "--warmup", "3"], cwd=REPO, capture_output=True, text=True, timeout=600)
+                        "--warmup", "3", "--full"], cwd=REPO, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -68,7 +69,7 @@ def test_bench_two_rank_flow_rehearsal(gpu):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                         str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2",
-                        "--steps", "10", "--warmup", "2"], cwd=REPO, env=env,
+                        "--steps", "10", "--warmup", "2", "--full"], cwd=REPO, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -89,7 +90,7 @@ def test_bench_two_rank_xgmi_rehearsal(gpu):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                         str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2",
-                        "--steps", "24", "--warmup", "4"], cwd=REPO, env=env,
+                        "--steps", "24", "--warmup", "4", "--full"], cwd=REPO, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -105,7 +106,7 @@ def test_bench_self_spawn_rehearsal(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2",
-                        "--steps", "20", "--warmup", "5"], cwd=REPO, env=env,
+                        "--steps", "20", "--warmup", "5", "--full"], cwd=REPO, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -204,3 +205,39 @@ def test_bench_emulated_rank_pricing(gpu):
     assert c["emulated_world_size"] == 8 and c["fc1_update_sharded"] is True
     assert c["grad_transport"] == "rccl-zero" and c["batch_per_rank"] == 32
     assert d["value"] > 0
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(gpu, tmp_path):
+    """A plain run (no --full) measures the headline configuration alone, and --dump-outputs
+    writes what the last timed step left (fp32 master weights, momentum, fp64 train metrics).
+    A second run with the same arguments trains on the same inputs: the step kernels sum in
+    a fixed order, so the arrays are equal bit for bit."""
+    import numpy as np
+    from pytorch_distributed_mnist_amd.models.specs import get_spec
+    outs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                            "--steps", "20", "--warmup", "3", "--dump-outputs",
+                            str(tmp_path / name)], cwd=REPO, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["scaling"] == "weak" and "strong" not in d
+        assert d["steps"] == 20 and d["ms_per_step"] > 0 and d["dtype"] == "bf16"
+        assert d["config"]["images_timed"] == 19 * 256 + 96
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["momentum_buffer.npy", "params.npy", "train_metrics.npy"]
+        outs.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = outs
+    total = get_spec("cnn").total
+    for f in ("params.npy", "momentum_buffer.npy"):
+        assert a[f].dtype == np.float32 and a[f].shape == (total,)
+        assert np.isfinite(a[f]).all() and np.abs(a[f]).max() > 0
+    m = a["train_metrics.npy"]
+    assert m.dtype == np.float64 and m.shape == (3,)
+    # [loss sum, correct, count] over every step since start-up: 3 warm-up + 20 timed
+    assert m[2] == 22 * 256 + 96 and 0 <= m[1] <= m[2] and m[0] > 0
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f

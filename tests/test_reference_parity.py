@@ -1,12 +1,15 @@
 """Parity against the reference itself (SURVEY.md §4.3 "Reference parity").
 
-The unmodified reference script (/root/reference/multi_proc_single_gpu.py, read-only) is run
-on CPU/gloo with the torchvision stand-in in tests/refshim, and this
-framework's CLI is run on the same IDX files from the same initial checkpoint.  Both resume
-from that checkpoint (reference S:196-214), train and evaluate, and print the reference's
-stdout contract (S:183, S:199-214, S:238-242); the printed lines must be identical and the
-written checkpoints must agree.
+The unmodified reference script was run on CPU/gloo with the torchvision stand-in in
+tests/refshim; what it printed and the checkpoints it wrote are stored
+under tests/golden/reference_parity/ (`python tests/test_reference_parity.py SCRIPT` records
+them again from a copy of the reference's multi_proc_single_gpu.py).  This framework's CLI is
+run on the same IDX files from the same initial checkpoint.  Both resume from that checkpoint
+(reference S:196-214), train and evaluate, and print the reference's stdout contract (S:183,
+S:199-214, S:238-242); the printed lines must be identical and the written checkpoints must
+agree.
 """
+import json
 import os
 import shutil
 import subprocess
@@ -18,10 +21,10 @@ import torch
 
 from conftest import REPO, free_port
 
-REF_SCRIPT = "/root/reference/multi_proc_single_gpu.py"
-SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "refshim")
-
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_SCRIPT), reason="reference not mounted")
+HERE = os.path.dirname(os.path.abspath(__file__))
+SHIM = os.path.join(HERE, "refshim")
+GOLDEN = os.path.join(HERE, "golden", "reference_parity")
+CASES = {1: 2, 2: 1}             # world size -> epochs
 
 
 def _write_data(root, n_train, n_test):
@@ -50,26 +53,64 @@ def _run(cmd, cwd, env_extra, timeout=600):
     return [l for l in r.stdout.splitlines() if not l.startswith("Namespace(")]
 
 
-def _compare(tmp_path, ws, epochs):
+def _setup(tmp_path):
     data = tmp_path / "data"
     _write_data(str(data), 2048, 512)
     ck = tmp_path / "init.pth.tar"
     _init_checkpoint(str(ck))
-    ref_dir, new_dir = tmp_path / "ref", tmp_path / "new"
-    ref_dir.mkdir()
+    return data, ck
+
+
+def _common(ws, epochs, data, ck):
+    return ["--world-size", str(ws), "--backend", "gloo", "--epochs", str(epochs),
+            "--root", str(data), "-j", "0", "--resume", str(ck)]
+
+
+def _lines(lines, ck):
+    """The printed lines with the initial checkpoint's (temporary) path taken out."""
+    return sorted(l.replace(str(ck), "<init>") for l in lines)
+
+
+def record(ref_script, tmp_path):
+    """Run the reference itself and store its lines and checkpoints as the golden files."""
+    data, ck = _setup(tmp_path)
+    for ws, epochs in CASES.items():
+        ref_dir = tmp_path / f"ref{ws}"
+        ref_dir.mkdir()
+        gold = os.path.join(GOLDEN, f"ws{ws}")
+        os.makedirs(gold, exist_ok=True)
+        ref = _run([sys.executable, ref_script] + _common(ws, epochs, data, ck)
+                   + ["-i", f"tcp://127.0.0.1:{free_port()}"],
+                   ref_dir, {"PYTHONPATH": SHIM, "FAKE_NGPU": str(ws)})
+        for e in range(epochs):
+            shutil.copy(ref_dir / "checkpoints" / f"checkpoint_{e}.pth.tar", gold)
+        ev = _run([sys.executable, ref_script, "--world-size", "1", "--backend", "gloo", "--root",
+                   str(data), "-j", "0", "--evaluate", "--resume",
+                   f"checkpoints/checkpoint_{epochs - 1}.pth.tar",
+                   "-i", f"tcp://127.0.0.1:{free_port()}"], ref_dir,
+                  {"PYTHONPATH": SHIM, "FAKE_NGPU": "1"})
+        with open(os.path.join(gold, "lines.json"), "w") as f:
+            json.dump({"train": _lines(ref, ck),
+                       "evaluate": [l for l in ev if l.startswith("test loss:")]}, f, indent=1)
+
+
+def _compare(tmp_path, ws, epochs):
+    assert CASES[ws] == epochs
+    data, ck = _setup(tmp_path)
+    gold = os.path.join(GOLDEN, f"ws{ws}")
+    with open(os.path.join(gold, "lines.json")) as f:
+        golden = json.load(f)
+    new_dir = tmp_path / "new"
     new_dir.mkdir()
-    common = ["--world-size", str(ws), "--backend", "gloo", "--epochs", str(epochs),
-              "--root", str(data), "-j", "0", "--resume", str(ck)]
-    ref = _run([sys.executable, REF_SCRIPT] + common + ["-i", f"tcp://127.0.0.1:{free_port()}"],
-               ref_dir, {"PYTHONPATH": SHIM, "FAKE_NGPU": str(ws)})
+    ref = golden["train"]
     new = _run([sys.executable, os.path.join(REPO, "multi_proc_single_gpu.py"), "--device", "cpu"]
-               + common + ["-i", f"tcp://127.0.0.1:{free_port()}"],
+               + _common(ws, epochs, data, ck) + ["-i", f"tcp://127.0.0.1:{free_port()}"],
                new_dir, {"PYTHONPATH": REPO})
     # same lines (ranks interleave, so compare as multisets)
-    assert sorted(ref) == sorted(new), "\n".join(["reference:"] + ref + ["new:"] + new)
+    assert ref == _lines(new, ck), "\n".join(["reference:"] + ref + ["new:"] + new)
     assert sum(l.startswith("Epoch:") for l in new) == ws * epochs
     for e in range(epochs):
-        a = torch.load(ref_dir / "checkpoints" / f"checkpoint_{e}.pth.tar", weights_only=True)
+        a = torch.load(os.path.join(gold, f"checkpoint_{e}.pth.tar"), weights_only=True)
         b = torch.load(new_dir / "checkpoints" / f"checkpoint_{e}.pth.tar", weights_only=True)
         assert a["epoch"] == b["epoch"] and a["best_acc"] == b["best_acc"]
         for k in a["state_dict"]:
@@ -83,19 +124,15 @@ def _compare(tmp_path, ws, epochs):
         pa = {k: v for k, v in a["optimizer"]["param_groups"][0].items()}
         pb = {k: v for k, v in b["optimizer"]["param_groups"][0].items()}
         assert pa == pb
-    # --evaluate on the final checkpoint prints the same line in both
-    last = f"checkpoints/checkpoint_{epochs - 1}.pth.tar"
-    ev_ref = _run([sys.executable, REF_SCRIPT, "--world-size", "1", "--backend", "gloo", "--root",
-                   str(data), "-j", "0", "--evaluate", "--resume", last,
-                   "-i", f"tcp://127.0.0.1:{free_port()}"], ref_dir,
-                  {"PYTHONPATH": SHIM, "FAKE_NGPU": "1"})
+    # --evaluate on the reference's final checkpoint prints the line the reference printed
+    last = os.path.join(gold, f"checkpoint_{epochs - 1}.pth.tar")
     ev_new = _run([sys.executable, os.path.join(REPO, "multi_proc_single_gpu.py"), "--device", "cpu",
                    "--world-size", "1", "--backend", "gloo", "--root", str(data), "-j", "0",
-                   "--evaluate", "--resume", os.path.join(str(ref_dir), last),
+                   "--evaluate", "--resume", last,
                    "-i", f"tcp://127.0.0.1:{free_port()}"], new_dir, {"PYTHONPATH": REPO})
-    t_ref = [l for l in ev_ref if l.startswith("test loss:")]
+    t_ref = golden["evaluate"]
     t_new = [l for l in ev_new if l.startswith("test loss:")]
-    assert len(t_ref) == 1 and t_ref == t_new, (ev_ref, ev_new)
+    assert len(t_ref) == 1 and t_ref == t_new, (t_ref, ev_new)
 
 
 def test_reference_parity_ws1(tmp_path):
@@ -105,3 +142,10 @@ def test_reference_parity_ws1(tmp_path):
 @pytest.mark.slow
 def test_reference_parity_ws2(tmp_path):
     _compare(tmp_path, ws=2, epochs=1)
+
+
+if __name__ == "__main__":
+    import pathlib
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        record(os.path.abspath(sys.argv[1]), pathlib.Path(d))

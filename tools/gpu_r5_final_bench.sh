@@ -23,7 +23,7 @@ PDM_FORCE_COMM=1 PDM_EMULATE_WS=8 PDM_RCCL_MODE=zero PDM_COMM=rccl run python be
 for B in 4096 8192; do
   run python bench.py --scaling weak --batch-per-rank $B --train-size 262144 --steps 40 --warmup 8
 done
-PDM_SHARE_DEVICE=1 PDM_BENCH_BACKEND=gloo run python bench.py --gpus 2 --steps 20 --warmup 5
+PDM_SHARE_DEVICE=1 PDM_BENCH_BACKEND=gloo run python bench.py --gpus 2 --steps 20 --warmup 5 --full
 tr() {   # name args...
   local name=$1; shift
   local d=$O/tr_$name

@@ -22,7 +22,7 @@ for B in 32 64; do
   run python bench.py --scaling weak --batch-per-rank $B
   PDM_FORCE_COMM=1 run python bench.py --scaling weak --batch-per-rank $B
 done
-PDM_SHARE_DEVICE=1 PDM_BENCH_BACKEND=gloo run python bench.py --gpus 2 --steps 20 --warmup 5
+PDM_SHARE_DEVICE=1 PDM_BENCH_BACKEND=gloo run python bench.py --gpus 2 --steps 20 --warmup 5 --full
 for B in 256 32; do
   d=$O/trace_$B
   timeout -k 10 120 rocprofv3 --kernel-trace -d $d -o run -- python3 bench.py --scaling weak --batch-per-rank $B --steps 200 --warmup 30 > /dev/null 2>&1 || exit 1

@@ -240,6 +240,62 @@ def test_cnn_step_gradients_match_autograd(gpu, B):
     assert abs(m[0].item() / B - loss.item()) < 2e-2 * max(1.0, loss.item())
     assert m[2].item() == B
     assert int(prog.gpu.ctr[0].item()) == 1 and int(prog.optimizer._step_dev.item()) == 1
+    # the train `correct` count against the argmax of the mirrored logits.  At the initial
+    # weights a quarter to a third of the rows have their two largest logits within 1e-2 (the
+    # bf16 scale) of each other, so the same batch is stepped once more with fc2.weight
+    # scaled by 128 (fp32, read by cnn_head alone; lr = 0, so nothing else has changed): an
+    # exact power of two, so the mirrored logits follow from the ones above
+    k = 128.0
+    prog.gpu.P["fc2.weight"].mul_(k)
+    prog.set_train_indices(idx)                    # a new epoch in the same order: the same rows again
+    prog.gpu.begin_epoch()
+    prog.metrics.reset(0)
+    prog.gpu.train_step(B)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        b2 = tp["fc2.bias"]
+        klog = k * (bf16_mirrored_forward(tp, x) - b2) + b2
+    top2 = klog.topk(2, dim=1).values
+    near = int(((top2[:, 0] - top2[:, 1]) < 1e-2).sum())
+    assert near <= 0.02 * B, near                              # from the reference alone
+    ref_correct = int(klog.argmax(1).eq(train.labels[sel]).sum())
+    m = prog.metrics.buf[0:3].cpu()
+    assert m[2].item() == B
+    assert 0 < ref_correct < B
+    assert abs(m[1].item() - ref_correct) <= near, (m[1].item(), ref_correct, near)
+
+
+def test_cnn_eval_ragged_chunks_after_training(gpu):
+    """evaluate() after one epoch of SGD-momentum (logits spread, so the labels matter) over
+    2048 + 37 test images: two EVAL_CHUNK chunks, the second with 37 rows (another fc1 block
+    count under the same split-K, a last head row group with 1 valid row of 4), against
+    bf16_mirrored_forward on the trained parameters read back from the arena -- it differs
+    from the kernel chain in fp32 summation order and rare bf16 rounding ties only.
+    Measured on MI355X: loss 1.488062 against 1.488062 (7.6e-08 relative, bound 2e-3), correct
+    1117 against 1117, 16 of the 2085 reference rows within 1e-2 (bound 41)."""
+    from pytorch_distributed_mnist_amd.runtime.cnn_step import EVAL_CHUNK
+    train = synthetic_split(640, True)
+    test = synthetic_split(EVAL_CHUNK + 37, False)
+    prog = build_local_program("cnn", "bf16", "cuda", 64, train, test, optimizer="sgd", lr=0.05,
+                               momentum=0.9, weight_decay=1e-4, seed=0, use_graphs=False)
+    prog.optimizer.sync_hyperparams()
+    prog.set_train_indices(distributed_indices(len(train), 1, 0, 0))
+    prog.train_epoch()
+    el, ea = prog.evaluate()
+    tp = _torch_params(prog)
+    with torch.no_grad():
+        logits = bf16_mirrored_forward(tp, normalize_reference(test.images))
+    top2 = logits.topk(2, dim=1).values
+    near = int(((top2[:, 0] - top2[:, 1]) < 1e-2).sum())
+    assert near <= 0.02 * len(test), near                      # from the reference alone
+    loss = F.cross_entropy(logits, test.labels).item()
+    correct = logits.argmax(1).eq(test.labels).sum().item()
+    print(f"\neval after training: loss {el.average:.6f} vs {loss:.6f} "
+          f"(rel {abs(el.average - loss) / loss:.1e}), correct {ea.correct} vs {correct}, near {near}")
+    assert el.count == len(test) == 2085
+    assert abs(el.average - loss) <= 2e-3 * loss
+    assert 0.2 * len(test) < correct < 0.9 * len(test)         # neither untrained nor saturated
+    assert abs(ea.correct - correct) <= near, (ea.correct, correct, near)
 
 
 def test_cnn_eval_matches_torch(gpu):

@@ -579,6 +579,89 @@ void cnn_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Te
                   train ? xg_step(xg) : nullptr, pdh32, cur_stream(part));
 }
 
+// ------------------------------------------------------------------ prediction
+// Outputs of the prediction heads (kernels.h): logp fp32 [>= B * 10], pred int32 [>= B];
+// confusion (int64 [10][10]) and metrics (fp64 [3]) are optional and need labels.
+struct PredictOut {
+  float* logp;
+  int32_t* pred;
+  int64_t* confusion;
+  double* metrics;
+};
+PredictOut check_predict_out(int64_t B, bool labelled, const at::Tensor& logp, const at::Tensor& pred,
+                             const c10::optional<at::Tensor>& confusion,
+                             const c10::optional<at::Tensor>& metrics) {
+  PredictOut o{};
+  need(logp, at::kFloat, "logp");
+  need_numel(logp, B * CNN_NCLS, "logp");
+  need(pred, at::kInt, "pred");
+  need_numel(pred, B, "pred");
+  o.logp = logp.data_ptr<float>();
+  o.pred = pred.data_ptr<int32_t>();
+  if (confusion.has_value() && confusion->defined()) {
+    TORCH_CHECK(labelled, "confusion needs labels");
+    need(*confusion, at::kLong, "confusion");
+    TORCH_CHECK(confusion->numel() == CNN_NCLS * CNN_NCLS, "confusion must be [10, 10]");
+    o.confusion = confusion->data_ptr<int64_t>();
+  }
+  if (metrics.has_value() && metrics->defined()) {
+    TORCH_CHECK(labelled, "metrics need labels");
+    need(*metrics, at::kDouble, "metrics");
+    need_numel(*metrics, 3, "metrics");
+    o.metrics = metrics->data_ptr<double>();
+  }
+  return o;
+}
+
+void cnn_predict_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
+                      at::Tensor bf2, c10::optional<at::Tensor> ylab, at::Tensor logp,
+                      at::Tensor pred, c10::optional<at::Tensor> confusion,
+                      c10::optional<at::Tensor> metrics) {
+  c10::DeviceGuard g(part.device());
+  TORCH_CHECK(B >= 1 && B <= INT32_MAX / (CNN_NCLS * 4), "B must be in [1, 2^31 / 40)");
+  TORCH_CHECK(splitk >= 1, "splitk must be >= 1");
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need_min(bf1, at::kFloat, CNN_HID, "bf1");
+  need_min(wf2, at::kFloat, CNN_NCLS * CNN_HID, "wf2");
+  need(bf2, at::kFloat, "bf2");
+  TORCH_CHECK(bf2.numel() == CNN_NCLS, "bf2");
+  const bool labelled = ylab.has_value() && ylab->defined();
+  if (labelled) {
+    need(*ylab, at::kInt, "ylab");
+    need_numel(*ylab, B, "ylab");
+  }
+  const PredictOut o = check_predict_out(B, labelled, logp, pred, confusion, metrics);
+  launch_cnn_predict_head(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
+                          wf2.data_ptr<float>(), bf2.data_ptr<float>(),
+                          labelled ? ylab->data_ptr<int32_t>() : nullptr, o.logp, o.pred,
+                          o.confusion, o.metrics, cur_stream(part));
+}
+
+void lin_predict(at::Tensor images, c10::optional<at::Tensor> labels, at::Tensor W, at::Tensor b,
+                 at::Tensor logp, at::Tensor pred, c10::optional<at::Tensor> confusion,
+                 c10::optional<at::Tensor> metrics) {
+  c10::DeviceGuard g(images.device());
+  need(images, at::kByte, "images");
+  need(W, at::kFloat, "W");
+  need(b, at::kFloat, "b");
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == 784, "images must be [N, 784]");
+  const int64_t n = images.size(0);
+  TORCH_CHECK(n <= INT32_MAX / LIN_K, "too many rows for one launch");
+  const bool labelled = labels.has_value() && labels->defined();
+  if (labelled) {
+    need(*labels, at::kInt, "labels");
+    TORCH_CHECK(labels->numel() == n, "labels must be [N]");
+  }
+  TORCH_CHECK(W.numel() == LIN_N * LIN_K && b.numel() == LIN_N, "W/b must be [10,784]/[10]");
+  need_aligned(images.data_ptr(), 16, "images");
+  need_aligned(W.data_ptr(), 16, "W");
+  const PredictOut o = check_predict_out(n, labelled, logp, pred, confusion, metrics);
+  if (n == 0) return;
+  launch_lin_predict(images.data_ptr<uint8_t>(), labelled ? labels->data_ptr<int32_t>() : nullptr,
+                     (int)n, W.data_ptr<float>(), b.data_ptr<float>(), o.logp, o.pred, o.confusion,
+                     o.metrics, cur_stream(images));
+}
+
 
 // fc_update (world size 1, optional): (kind, p, g, m, v or None, shadow, lr, step, beta1,
 // beta2, eps, wd, momentum, dampening, nesterov, grad_scale[, shadow_t_next]) -- the
@@ -917,6 +1000,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("train"), py::arg("dh"),
         py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
         py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none());
+  m.def("cnn_predict_head", &cnn_predict_head, py::arg("part"), py::arg("splitk"), py::arg("B"),
+        py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("logp"),
+        py::arg("pred"), py::arg("confusion") = py::none(), py::arg("metrics") = py::none());
+  m.def("lin_predict", &lin_predict, py::arg("images"), py::arg("labels"), py::arg("W"),
+        py::arg("b"), py::arg("logp"), py::arg("pred"), py::arg("confusion") = py::none(),
+        py::arg("metrics") = py::none());
   m.def("fc1_bwd", &fc1_bwd, py::arg("dh"), py::arg("dht"), py::arg("ldt"), py::arg("pool"),
         py::arg("wf1t"), py::arg("B"), py::arg("gwf1"), py::arg("dpool"), py::arg("head_slab"),
         py::arg("gwf2"), py::arg("gbf2"), py::arg("gbf1"), py::arg("metrics"),

@@ -255,6 +255,18 @@ void launch_f32_conv_bwd(const float* a1g, const float* xng, const float* dpool,
                          const uint8_t* pmask, const float* w2, int B, int ipb, float* slab,
                          bool x3, const float* w2x, hipStream_t st);
 
+// ---------------------------------------------------------------- prediction (predict.hip)
+// The inference twins of cnn_head<eval> / lin_eval: per-row outputs instead of three sums.
+// logp fp32 [B][10] (log-softmax), pred int32 [B] (first maximum); optional: ylab / labels,
+// and with them confusion int64 [10][10] (confusion[y][pred] += 1) and the evaluation head's
+// fp64 metrics[3] additions.  Rows >= B write nothing.
+void launch_cnn_predict_head(const float* part, int splitk, int B, const float* bf1,
+                             const float* wf2, const float* bf2, const int32_t* ylab, float* logp,
+                             int32_t* pred, int64_t* confusion, double* metrics, hipStream_t st);
+void launch_lin_predict(const uint8_t* images, const int32_t* labels, int n_total, const float* W,
+                        const float* b, float* logp, int32_t* pred, int64_t* confusion,
+                        double* metrics, hipStream_t st);
+
 // diagnostic timestamps (all zero unless built with PDM_STAMPS=1)
 void read_stamps_fwd(unsigned long long* host);
 void read_stamps_bwd(unsigned long long* host);

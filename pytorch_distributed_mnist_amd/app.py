@@ -221,6 +221,16 @@ def run(args):
         if args.evaluate:
             test_loss, test_acc = trainer.evaluate()
             out('test loss: {}, test acc: {}.'.format(test_loss, test_acc))
+            predict_out = getattr(args, "predict_out", None)
+            if predict_out:
+                # every rank runs the (unsharded) pass, as it runs the evaluation; rank 0 writes
+                # the file and prints the per-class lines
+                from .predict import class_lines, save_predictions
+                pred = program.predict()
+                if rank == 0:
+                    save_predictions(predict_out, pred, test_split.labels)
+                    for line in class_lines(pred.confusion):
+                        out(line)
             return
 
         # epoch e+1's sample order is computed on a host thread while epoch e trains

@@ -8,8 +8,8 @@ Additions are opt-in and default to the reference's behaviour:
 ``--arch {linear,cnn}``, ``--optimizer {adam,sgd}`` (sgd finally consumes
 ``--momentum``/``--wd`` as the commented-out reference code would,
 :192-194), ``--dtype {fp32,bf16}``, ``--synthetic``/``--synthetic-size``,
-``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``
-and ``--rank-prefix``.
+``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``,
+``--rank-prefix`` and ``--predict-out`` (with ``--evaluate``).
 """
 from __future__ import annotations
 
@@ -98,9 +98,20 @@ def build_parser() -> argparse.ArgumentParser:
                         '--marker-trace')
     g.add_argument('--rank-prefix', action='store_true',
                    help="prefix every per-rank line with '[rank r] '")
+    # (no default: the attribute exists only when the flag is given, so the Namespace line the
+    # app prints is unchanged without it)
+    g.add_argument('--predict-out', metavar='PATH', default=argparse.SUPPRESS,
+                   help='with --evaluate: after the test line, rank 0 writes PATH, a NumPy .npz '
+                        'with per-sample log_probs [N, 10], pred [N], labels [N] and the confusion '
+                        'matrix [10, 10] of the test set, and prints one accuracy line per class')
     parser.set_defaults(local_rank_given=False)
     return parser
 
 
 def parse_args(argv=None):
-    return build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    parser = build_parser()
+    args = parser.parse_args(sys.argv[1:] if argv is None else argv)
+    if hasattr(args, "predict_out") and not args.evaluate:
+        parser.error("--predict-out is only valid with --evaluate (it writes the predictions of "
+                     "the evaluation pass)")
+    return args

@@ -163,6 +163,30 @@ def load_split(root: str, train: bool, *, synthetic: bool = False,
     return synthetic_split(n, train, seed)
 
 
+def image_rows(images) -> torch.Tensor:
+    """Raw images as the kernels take them: uint8 [N, 784] on the host, from a torch tensor or
+    a NumPy array shaped [N, 28, 28] or [N, 784]."""
+    t = torch.from_numpy(np.ascontiguousarray(images)) if isinstance(images, np.ndarray) \
+        else torch.as_tensor(images)
+    if t.dtype != torch.uint8:
+        raise ValueError(f"images must be uint8 (raw pixels 0..255), got {t.dtype}")
+    if t.dim() < 2 or tuple(t.shape[1:]) not in ((IMAGE_HW, IMAGE_HW), (IMAGE_PIXELS,)) or t.shape[0] < 1:
+        raise ValueError(f"images must be [N, 28, 28] or [N, 784] with N >= 1, got {tuple(t.shape)}")
+    return t.reshape(t.shape[0], IMAGE_PIXELS).contiguous()
+
+
+def label_vector(labels, n: int) -> torch.Tensor:
+    """Class labels as int64 [n] on the host, from a torch tensor or a NumPy array."""
+    t = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) \
+        else torch.as_tensor(labels)
+    if t.dim() != 1 or t.shape[0] != n or t.is_floating_point():
+        raise ValueError(f"labels must be {n} integers, got {t.dtype} {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    if n and (int(t.min()) < 0 or int(t.max()) >= NUM_CLASSES):
+        raise ValueError(f"labels must lie in [0, {NUM_CLASSES})")
+    return t
+
+
 def normalize_reference(images_u8: torch.Tensor) -> torch.Tensor:
     """``Normalize(ToTensor(x))`` in fp32, exactly as torchvision computes it.
 

@@ -190,3 +190,24 @@ class CnnStepF32(GpuStepBase):
             C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
             C.cnn_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
                        False, None, None, 32, None, self.metrics.eval_view(), None, None)
+
+    def predict(self, images_u8, labels=None):
+        """evaluate()'s forward chain over any images, ending in the prediction head
+        (csrc/kernels/predict.hip) instead of the metric sums."""
+        C, P = self.C, self.P
+        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
+        n = images.shape[0]
+        # the forward copies its rows' labels to ylab either way: zeros without labels
+        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
+        for s in range(0, n, EVAL_CHUNK):
+            b = min(EVAL_CHUNK, n - s)
+            se = splitk_eval(b)
+            C.f32_fwd(images[s:s + b], flab[s:s + b], None, b, b,
+                      P["conv1.weight"], P["conv1.bias"], P["conv2.weight"], P["conv2.bias"],
+                      self.pool, None, None, None, self.ylab, x3=self.conv_x3,
+                      w2s=self.w2split)
+            C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
+            C.cnn_predict_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
+                               self.ylab if lab is not None else None, logp[s:s + b],
+                               pred[s:s + b], conf)
+        return logp, pred, conf

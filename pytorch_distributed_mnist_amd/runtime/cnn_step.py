@@ -682,3 +682,23 @@ class CnnStep(GpuStepBase):
             C.fc1_fwd(self.pool, self.wf1, self.part, b, S)
             C.cnn_head(self.part, S, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
                        False, None, None, 32, None, self.metrics.eval_view(), None, None)
+
+    def predict(self, images_u8, labels=None):
+        """evaluate()'s forward chain over any images, ending in the prediction head
+        (csrc/kernels/predict.hip) instead of the metric sums."""
+        C, P = self.C, self.P
+        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
+        n = images.shape[0]
+        # the forward copies its rows' labels to ylab either way: zeros without labels
+        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
+        S = self.splitk_eval
+        for s in range(0, n, EVAL_CHUNK):
+            b = min(EVAL_CHUNK, n - s)
+            C.cnn_fwd(images[s:s + b], flab[s:s + b], None, None, b, b,
+                      P["conv1.weight"], P["conv1.bias"], self.w2, P["conv2.bias"], self.pool,
+                      self.pmask, None, self.ylab)
+            C.fc1_fwd(self.pool, self.wf1, self.part, b, S)
+            C.cnn_predict_head(self.part, S, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
+                               self.ylab if lab is not None else None, logp[s:s + b],
+                               pred[s:s + b], conf)
+        return logp, pred, conf

@@ -60,6 +60,24 @@ def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, met
 
 
 @torch.no_grad()
+def predict_step_cpu(model: str, arena, images_u8, labels=None):
+    """What the model says about every row (the oracle of the GPU prediction heads):
+    (log_probs fp32 [N, 10], pred int64 [N], confusion int64 [10, 10] or None without labels;
+    confusion[y][pred] counts the rows of class y predicted as pred)."""
+    x = normalize_reference(images_u8)
+    views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}
+    logits = functional_forward(model, views, x)
+    log_probs = F.log_softmax(logits, dim=1)
+    pred = logits.argmax(dim=1)
+    confusion = None
+    if labels is not None:
+        ncls = logits.shape[1]
+        confusion = torch.bincount(labels.to(torch.int64) * ncls + pred,
+                                   minlength=ncls * ncls).view(ncls, ncls)
+    return log_probs, pred, confusion
+
+
+@torch.no_grad()
 def eval_step_cpu(model: str, arena, images_u8, labels, metrics_buf):
     x = normalize_reference(images_u8)
     views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}

@@ -426,6 +426,35 @@ class GpuStepBase:
         self.graphs.clear()
         self._opt_segments = None
 
+    # -- prediction --------------------------------------------------------------
+    def _predict_io(self, images_u8: torch.Tensor, labels):
+        """Device inputs and fresh outputs of ``predict``: (images uint8 [N, 784], labels int32
+        [N] or None, log_probs fp32 [N, 10], pred int32 [N], confusion int64 [10, 10] or None).
+        The outputs are allocated here, so this must not run inside a graph capture."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("predict() allocates its outputs: call it outside a graph capture")
+        dev = self.device
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 2 or images_u8.shape[1] != 784 \
+                or images_u8.shape[0] < 1:
+            raise ValueError("predict() takes uint8 images [N >= 1, 784], got "
+                             f"{images_u8.dtype} {tuple(images_u8.shape)}")
+        images = images_u8.to(dev).contiguous()
+        n = images.shape[0]
+        lab = None
+        if labels is not None:
+            if labels.numel() != n:
+                raise ValueError(f"{labels.numel()} labels for {n} images")
+            lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+        logp = torch.empty(n, 10, dtype=torch.float32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        conf = None if lab is None else torch.zeros(10, 10, dtype=torch.int64, device=dev)
+        return images, lab, logp, pred, conf
+
+    def predict(self, images_u8: torch.Tensor, labels=None):
+        """(log_probs, pred, confusion | None) of any N >= 1 images, on the device; enqueued on
+        the current stream (the caller synchronises before reading)."""
+        raise NotImplementedError
+
 
 class LinearStep(GpuStepBase):
     """Reference Net step.  world size 1: lin_train -> optim (the optimizer sums the
@@ -485,3 +514,8 @@ class LinearStep(GpuStepBase):
     def evaluate(self) -> None:
         self.C.lin_eval(self.test_images, self.test_labels, self.W, self.b,
                         self.metrics.eval_view())
+
+    def predict(self, images_u8, labels=None):
+        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
+        self.C.lin_predict(images, lab, self.W, self.b, logp, pred, conf)
+        return logp, pred, conf

@@ -16,14 +16,31 @@ On the CPU (gloo path) the same program runs the torch reference step.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
 
+from ..data.mnist import image_rows, label_vector
 from ..data.sampler import batch_bounds
 from ..utils.metrics import DeviceMetrics
-from .cpu_step import eval_step_cpu, train_step_cpu
+from .cpu_step import eval_step_cpu, predict_step_cpu, train_step_cpu
 from .structure import StepStructure
+
+
+# rows per CPU forward of predict(): a constant, not the program's batch size, so that the same
+# weights give the same bits whichever program (trainer or load_predictor) holds them
+PREDICT_BATCH_CPU = 256
+
+
+@dataclass
+class Prediction:
+    """What ``TrainProgram.predict`` returns, on the host: log_probs fp32 [N, 10] (log-softmax
+    of the logits), pred int64 [N] (argmax, first maximum) and, with labels, confusion int64
+    [10, 10] (confusion[y][p] = rows of class y predicted as p), else None."""
+    log_probs: torch.Tensor
+    pred: torch.Tensor
+    confusion: Optional[torch.Tensor]
 
 
 class TrainProgram:
@@ -189,6 +206,35 @@ class TrainProgram:
                 eval_step_cpu(self.model, self.arena, self.test_split.images[start:start + size],
                               self.test_split.labels[start:start + size], buf)
         return self.metrics.read(DeviceMetrics.EVAL)
+
+    @torch.no_grad()
+    def predict(self, images=None, labels=None) -> Prediction:
+        """Per-sample predictions of the current weights: for ``images`` (uint8 [N, 28, 28] or
+        [N, 784], torch or NumPy, any N >= 1; ``labels`` optional), or with no arguments for the
+        test split and its labels.  Runs evaluate()'s forward; the metric accumulators are not
+        touched."""
+        if images is None:
+            if labels is not None:
+                raise ValueError("labels without images")
+            if self.gpu is not None:       # the device-resident copy of the test split
+                images, labels = self.gpu.test_images, self.gpu.test_labels
+            else:
+                images, labels = self.test_split.images, self.test_split.labels
+        else:
+            images = image_rows(images)
+            if labels is not None:
+                labels = label_vector(labels, images.shape[0])
+        if self.gpu is not None:
+            logp, pred, conf = self.gpu.predict(images, labels)
+            if self.sync_fn is not None:
+                self.sync_fn("prediction")
+            return Prediction(logp.cpu(), pred.cpu().to(torch.int64),
+                              None if conf is None else conf.cpu())
+        outs = [predict_step_cpu(self.model, self.arena, images[start:start + size],
+                                 None if labels is None else labels[start:start + size])
+                for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)]
+        return Prediction(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
+                          None if labels is None else sum(o[2] for o in outs))
 
 
 def build_local_program(arch: str, dtype: str, device, batch_size: int, train_split, test_split,

@@ -1,14 +1,393 @@
-"""Fused optimizer kernel vs the flat CPU optimizer (torch op order)."""
+"""Fused optimizer kernel (csrc/kernels/optim.hip): every segment path against fp64.
+
+The first two tests compare whole arenas with the flat CPU optimizer (torch op order).  The
+rest call ``optim_step`` on small flat tensors and pin each code path of ``optim_kernel`` --
+plain (vector chunk + scalar tail), plain with ``shadow`` / ``shadow_lo``, the transposed-shadow
+tile with its vector and scalar fall-backs, transpose-only, slab-reduced -- to ``ref_update``,
+an fp64 evaluation of ``optim_common.h update<>`` on the fp32 inputs the kernel read.
+
+Error measure, per output x in (p, m, v):  e(x) = max_i |x_i - ref_i| / scale_i,  where scale
+is the *condition scale* of the formula (every operand replaced by its absolute value, every
+subtraction by an addition).  Two assertions:
+
+1. e(kernel) <= 8 x e(cpu32), cpu32 = ``FlatSGD.step_cpu`` / ``FlatAdam.step_cpu`` in fp32 on
+   the same inputs (the project's own fp32 arithmetic; the margin of test_gpu_cnn_head.py and
+   test_gpu_cnn_f32_kernels.py);
+2. e(kernel) <= R * 2^-23, R = the fp32 roundings on the longest chain of that output, counted
+   from ``update<>`` by ``roundings()`` below (each rounding is at most 2^-24 of the condition
+   scale, so the bound has a factor 2 in hand).
+
+Hyper-parameters enter the reference as the kernel sees them: ``float(beta)``, ``float(lr)``,
+``1.f - beta`` formed in fp32; the bias corrections from Python doubles.  That is also where
+the kernel and torch differ: torch rounds the *double* ``1 - beta`` to fp32 (``lerp_`` weight
+0.1f, ``addcmul_`` value 0.001f), the kernel subtracts ``float(beta)`` from 1.f (0.100000024,
+0.00099998713): Adam's ``exp_avg_sq`` increment is 1.3e-5 smaller, relatively, than
+``step_cpu``'s (e(cpu32) of v below), so Adam is *not* bit-identical to the CPU path, and
+assertion 2 is the binding one for Adam.
+
+Shadows are bit for bit from the kernel's own returned p (``bf16(p)`` in row-major,
+``frag_major`` and transposed orders, ``shadow_lo == bf16(p - float(bf16(p)))``).  Every output
+buffer is over-allocated by guard regions filled with a sentinel (NaN / 0x7fc1) which must
+survive, and arena elements outside every segment must keep their bits in p, g, m and v.
+
+Measured on MI355X (max over the cases of a path; "differ" = share of p elements not bit-equal
+to ``step_cpu``; R of the worst case shown):
+
+    path            out  e(kernel)  e(cpu32)  ratio   R  e/(R 2^-23)  differ
+    plain, SGD      p    1.46e-07   1.07e-07  2.20    7  0.22         1.4 % .. 12 %
+                    m    1.25e-07   1.06e-07  1.35    4  0.30
+    plain, Adam     p    2.12e-07   2.35e-05  0.52   15  0.13         0.5 % .. 100 %
+                    m    1.33e-07   3.11e-07  1.57    5  0.27
+                    v    2.05e-07   4.69e-05  0.02    7  0.25
+    tile, SGD       p    1.71e-07   1.29e-07  1.79    6  0.24         5 % .. 13 %
+                    m    1.15e-07   1.15e-07  1.00    4  0.24
+    tile, Adam      p    1.57e-07   4.89e-06  1.00   15  0.09         0 % .. 1.5 %
+                    m    1.68e-07   3.48e-07  0.53    5  0.28
+                    v    2.28e-07   1.31e-05  0.14    7  0.27
+    shadow_lo, SGD  p    1.19e-07   9.86e-08  1.55    6  0.17         5.9 %
+    shadow_lo, Adam p    9.28e-08   2.87e-06  0.10   15  0.05         1.2 %
+    slab, SGD       p    1.47e-07   1.21e-07  1.62    6  0.21         0 % .. 40 %
+                    m    1.13e-07   1.13e-07  1.00    4  0.24
+    slab, Adam      p    8.32e-08   3.64e-06  1.00   15  0.05         0 % .. 30 %
+                    m    1.67e-07   3.56e-07  0.47    5  0.28
+                    v    2.03e-07   1.31e-05  0.03    7  0.24
+    table of 8      p    1.18e-07   1.18e-07  1.28    6  0.16         0 % .. 13 %
+
+The ratio column is the largest e(kernel) / e(cpu32) of any case (where e(cpu32) > 0), not the
+quotient of the two maxima.  The kernel's figures equal an op-by-op fp32 evaluation of
+update<> on the CPU, to the digit.  "differ" is not 0 for SGD either: ATen's CPU
+``add(alpha=...)`` contracts to an FMA where the kernel (contraction off) rounds twice, so
+"bit-for-bit with torch on the CPU" holds for 60 % to 100 % of the elements of an SGD case
+and, for Adam, for anything between none and all of them (the float(beta) note above).
+Neither is asserted.
+
+Mutations tried on scratch builds (each fails new tests; "old" = the parent's suite):
+h.first forced to 0 (old: passes), nesterov branch dropped (old: passes), bc2_sqrt from
+beta1_d (old: fails), shadow_lo = bf16(p) (old: passes), slab loop stride 16 * 4 (old: passes).
+"""
+import math
+import types
+
 import pytest
 import torch
 
 from pytorch_distributed_mnist_amd.models import get_spec
 from pytorch_distributed_mnist_amd.optim import FlatAdam, FlatSGD
 from pytorch_distributed_mnist_amd.runtime.arena import FlatArena
+from pytorch_distributed_mnist_amd.runtime.cnn_step import frag_major, frag_major_t
 
 pytestmark = pytest.mark.gpu
 
+F32, F64, BF = torch.float32, torch.float64, torch.bfloat16
+U23 = 2.0 ** -23
+GUARD = 64            # elements of sentinel on either side of every device buffer
 
+
+def _C():
+    from pytorch_distributed_mnist_amd.ops import _ext
+    return _ext.require()
+
+
+# ------------------------------------------------------------------ the fp64 reference
+def f32(x):
+    """The double value of float(x) as the kernel holds it."""
+    return torch.tensor(float(x), dtype=F32).item()
+
+
+def sgd(lr=0.05, mom=0.0, wd=0.0, damp=0.0, nesterov=False, gs=1.0):
+    return dict(lr=lr, mom=mom, wd=wd, damp=damp, nesterov=nesterov, gs=gs)
+
+
+def adam(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, wd=0.0, gs=1.0):
+    return dict(lr=lr, betas=tuple(betas), eps=eps, wd=wd, gs=gs)
+
+
+def ref_update(kind, p0, g, m0, v0, h, step):
+    """optim_common.h update<> in fp64 on the fp32 inputs.  Returns {name: (value, scale)} for
+    p, m (and v for Adam); scale is the condition scale of the same formula."""
+    p0, g, m0 = p0.to(F64), g.to(F64), m0.to(F64)
+    gs, wd = f32(h["gs"]), f32(h["wd"])
+    g = gs * g
+    G = g.abs()
+    if wd != 0:
+        g = g + wd * p0
+        G = G + wd * p0.abs()
+    if kind == "sgd":
+        lr, mom = f32(h["lr"]), f32(h["mom"])
+        omd = f32(1.0 - f32(h["damp"]))               # 1.f - h.damp
+        if mom != 0:
+            if step <= 1:
+                m, M = g.clone(), G.clone()
+            else:
+                m = m0 * mom + omd * g
+                M = m0.abs() * mom + omd * G
+            d, D = (g + mom * m, G + mom * M) if h["nesterov"] else (m, M)
+        else:
+            m, M, d, D = m0, m0.abs(), g, G
+        return {"p": (p0 - lr * d, p0.abs() + lr * D), "m": (m, M)}
+    v0 = v0.to(F64)
+    b1, b2, eps = f32(h["betas"][0]), f32(h["betas"][1]), f32(h["eps"])
+    w = f32(1.0 - b1)                                  # 1.f - h.beta1
+    if w < 0.5:
+        m = m0 + w * (g - m0)
+        M = m0.abs() + w * (G + m0.abs())
+    else:
+        omw = f32(1.0 - w)
+        m = g - (g - m0) * omw
+        M = G + (G + m0.abs()) * omw
+    omb2 = f32(1.0 - b2)                               # 1.f - h.beta2
+    v = v0 * b2 + omb2 * g * g
+    V = v0.abs() * b2 + omb2 * G * G
+    bc1 = 1.0 - h["betas"][0] ** step                  # Python doubles, as torch
+    bc2 = 1.0 - h["betas"][1] ** step
+    step_size = f32(h["lr"] / bc1)
+    bc2_sqrt = f32(math.sqrt(bc2))
+    denom = v.sqrt() / bc2_sqrt + eps
+    return {"p": (p0 - step_size * (m / denom), p0.abs() + step_size * (M / denom)),
+            "m": (m, M), "v": (v, V)}
+
+
+def roundings(kind, h, step):
+    """R: fp32 roundings on the longest chain of each output of update<>.
+    g: `g *= gs` (1) and `fmaf(wd, p, g)` (1, with wd).
+    SGD m: first step m = g; else `(1.f - damp) * d` (1) and the sum (1) on top of g (the
+    `m * mom` branch is shorter).  d: nesterov adds `mom * m` (1) and `d + ...` (1).
+    p: `(-lr) * d` (1) and `p + ...` (1).  With wd, momentum and nesterov: 2 + 2 + 2 + 2 = 8.
+    Adam m: `g - m` (1), `w * (...)` (1), `m + ...` (1) on top of g: 5 with wd.
+    v: `(1.f - beta2) * g` (1), `* g` (1), the sum (1), and g's own roundings count twice (g
+    is squared): 2 * 2 + 3 = 7.  denom: sqrtf halves v's relative error and rounds once,
+    `/ bc2_sqrt` (1), `+ eps` (1).  p: the quotient m / denom carries both chains, then the
+    division (1), `(-step_size) * ...` (1) and `p + ...` (1): 5 + 7 + 3 = 15 with wd."""
+    rg = 1 + (f32(h["wd"]) != 0)
+    if kind == "sgd":
+        if f32(h["mom"]) != 0:
+            rm = rg if step <= 1 else rg + 2
+            rd = rm + 2 if h["nesterov"] else rm
+        else:
+            rm, rd = 0, rg
+        return {"p": rd + 2, "m": rm}
+    rm, rv = rg + 3, 2 * rg + 3
+    rden = math.ceil(rv / 2) + 3
+    return {"p": rm + rden + 3, "m": rm, "v": rv}
+
+
+def cpu32_update(kind, p0, g, m0, v0, h, step):
+    """FlatSGD.step_cpu / FlatAdam.step_cpu in fp32 on the same inputs."""
+    ar = types.SimpleNamespace(params=p0.clone(), grads=g.clone(), device=torch.device("cpu"))
+    if kind == "sgd":
+        o = FlatSGD(ar, lr=h["lr"], momentum=h["mom"], weight_decay=h["wd"],
+                    dampening=h["damp"], nesterov=h["nesterov"])
+        o.momentum_buffer.copy_(m0)
+        out = {"m": o.momentum_buffer}
+    else:
+        o = FlatAdam(ar, lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["wd"])
+        o.exp_avg.copy_(m0)
+        o.exp_avg_sq.copy_(v0)
+        out = {"m": o.exp_avg, "v": o.exp_avg_sq}
+    o.step_count = step - 1
+    o.step_cpu(grad_scale=h["gs"])
+    out["p"] = ar.params
+    return out
+
+
+def err(x, ref, scale):
+    """max_i |x_i - ref_i| / scale_i (0 / 0 = 0; a NaN in x gives NaN, which fails any <=)."""
+    d = (x.to(F64) - ref).abs()
+    e = torch.where(scale > 0, d / scale.clamp_min(1e-300),
+                    torch.where(d == 0, torch.zeros_like(d), torch.full_like(d, math.inf)))
+    return e.max().item() if not torch.isnan(e).any() else math.nan
+
+
+def bits(t):
+    return t.view(torch.int32 if t.dtype == F32 else torch.int16)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+
+
+def measure(tag, kind, h, step, p0, g, m0, v0, got):
+    """The two assertions for one segment's outputs.  Prints one line per output (collected
+    into the docstring's table)."""
+    ref = ref_update(kind, p0, g, m0, v0, h, step)
+    c32 = cpu32_update(kind, p0, g, m0, v0, h, step)
+    R = roundings(kind, h, step)
+    differ = (bits(got["p"]) != bits(c32["p"])).double().mean().item()
+    res = {}
+    for k, (val, scale) in ref.items():
+        ek, ec = err(got[k], val, scale), err(c32[k], val, scale)
+        res[k] = (ek, ec)
+        print(f"UPD {tag} {kind} step={step} {k}: e(kernel)={ek:.3e} e(cpu32)={ec:.3e} "
+              f"ratio={ek / ec if ec > 0 else (0.0 if ek == 0 else math.inf):.2f} R={R[k]} "
+              f"differ={differ:.4f}")
+    for k, (ek, ec) in res.items():
+        assert ek <= 8 * ec, (tag, kind, k, ek, ec)
+        assert ek <= R[k] * U23, (tag, kind, k, ek, R[k])     # R from roundings()
+    return res
+
+
+# ------------------------------------------------------------------ device buffers
+def sentinel(n, dtype):
+    if dtype == BF:
+        return torch.full((n,), 0x7fc1, dtype=torch.int16).view(BF)
+    return torch.full((n,), math.nan, dtype=dtype)
+
+
+class Guarded:
+    """A device buffer with GUARD sentinel elements on either side of the payload."""
+
+    def __init__(self, host, gpu):
+        self.n, self.dtype = host.numel(), host.dtype
+        buf = sentinel(self.n + 2 * GUARD, host.dtype)
+        bits(buf)[GUARD:GUARD + self.n] = bits(host.reshape(-1))
+        self.buf = buf.to(gpu)
+        self.view = self.buf[GUARD:GUARD + self.n]
+
+    def read(self):
+        out = self.buf.cpu()
+        s = sentinel(GUARD, self.dtype)
+        assert same_bits(out[:GUARD], s) and same_bits(out[GUARD + self.n:], s), "guard overwritten"
+        return out[GUARD:GUARD + self.n].clone()
+
+
+def launch(C, gpu, kind, h, step, p, g, m, v, segs, **kw):
+    lr = torch.tensor([h["lr"]], dtype=F64, device=gpu)
+    st = torch.tensor([step], dtype=torch.int64, device=gpu)
+    if kind == "adam":
+        C.optim_step(C.OPT_ADAM, p, g, m, v, lr, st, h["betas"][0], h["betas"][1], h["eps"],
+                     h["wd"], 0.0, 0.0, False, h["gs"], segs, **kw)
+    else:
+        C.optim_step(C.OPT_SGD, p, g, m, None, lr, st, 0.0, 0.0, 0.0, h["wd"], h["mom"],
+                     h["damp"], h["nesterov"], h["gs"], segs, **kw)
+    torch.cuda.synchronize()
+
+
+def slab_sum(slab, col0, numel):
+    """The documented slab reduction in fp32: group rg adds slabs rg, rg + 16, ... in ascending
+    order from 0, then the 16 group sums are added in order 0..15 from 0."""
+    x = slab[:, col0:col0 + numel]
+    tot = torch.zeros(numel, dtype=F32)
+    for rg in range(16):
+        acc = torch.zeros(numel, dtype=F32)
+        for j in range(rg, x.shape[0], 16):
+            acc = acc + x[j]
+        tot = tot + acc
+    return tot
+
+
+def seg(off, rows, cols, sh=None, sht=None, lo=False, tonly=False, slab=None):
+    """sh / sht: None, "row" or "frag"; slab: (nslab, col0, stride)."""
+    return dict(off=off, rows=rows, cols=cols, sh=sh, sht=sht, lo=lo, tonly=tonly, slab=slab)
+
+
+def layout(pb, rows, cols, how, transposed):
+    w = pb.view(rows, cols)
+    if transposed:
+        return frag_major_t(w) if how == "frag" else w.t().contiguous().reshape(-1)
+    return frag_major(w) if how == "frag" else w.reshape(-1)
+
+
+def run_segments(gpu, kind, h, step, total, specs, seed, tag, pscale=1.0, gscale=1.0,
+                 zero_state=False, patch=None, metrics=None, check=True):
+    """One optim_step launch over `specs` on a poisoned, guarded arena of `total` elements;
+    checks every segment against ref_update, every shadow bit for bit, the guards, the gaps
+    and the bump counter.  patch(p0, g0): in-place edit of the inputs before the upload."""
+    C = _C()
+    gen = torch.Generator().manual_seed(seed)
+    rn = lambda n: torch.randn(n, generator=gen)
+    p0, g0 = rn(total) * pscale, rn(total) * gscale
+    g0[::16] = 0.0                                   # a sixteenth of the gradients exactly 0
+    m0, v0 = rn(total) * (0.5 * gscale), (rn(total) * gscale) ** 2
+    if zero_state:
+        m0.zero_()
+        v0.zero_()
+    if patch is not None:
+        patch(p0, g0)
+    nanf = math.nan
+    segs, aux = [], []
+    for sp in specs:
+        n, sl = sp["rows"] * sp["cols"], slice(sp["off"], sp["off"] + sp["rows"] * sp["cols"])
+        a = {}
+        if sp["tonly"]:
+            for t in (p0, g0, m0, v0):
+                t[sl] = nanf                         # an update of this segment would show
+            a["src"] = rn(n).to(BF)
+            a["sh"] = Guarded(a["src"], gpu)
+        elif sp["sh"]:
+            a["sh"] = Guarded(sentinel(n, BF), gpu)
+        if sp["sht"]:
+            a["sht"] = Guarded(sentinel(n, BF), gpu)
+        if sp["lo"]:
+            a["lo"] = Guarded(sentinel(n, BF), gpu)
+        st = None
+        if sp["slab"]:
+            nslab, col0, stride = sp["slab"]
+            slab = torch.full((nslab, stride), nanf)   # columns of other segments: poison
+            slab[:, col0:col0 + n] = torch.randn(nslab, n, generator=gen) * gscale
+            slab[:, col0:col0 + n:16] = 0.0
+            g0[sl] = nanf                            # the kernel overwrites it with the sum
+            a["slab"] = slab
+            st = (slab.reshape(-1).to(gpu), nslab, col0, stride)
+        segs.append((sp["off"], sp["rows"], sp["cols"], a["sh"].view if "sh" in a else None,
+                     a["sht"].view if "sht" in a else None, st, sp["tonly"], sp["sht"] == "frag",
+                     sp["sh"] == "frag", a["lo"].view if "lo" in a else None))
+        aux.append(a)
+    P, G, M = Guarded(p0, gpu), Guarded(g0, gpu), Guarded(m0, gpu)
+    V = Guarded(v0, gpu) if kind == "adam" else None
+    bump = torch.tensor([41], dtype=torch.int64, device=gpu)
+    kw = {"bump": bump}
+    if metrics is not None:
+        kw["metrics"] = metrics
+    launch(C, gpu, kind, h, step, P.view, G.view, M.view, V.view if V else None, segs, **kw)
+    assert bump.item() == 42
+    got = {"p": P.read(), "g": G.read(), "m": M.read()}
+    ins = {"p": p0, "g": g0, "m": m0}
+    if V:
+        got["v"], ins["v"] = V.read(), v0
+    covered = torch.zeros(total, dtype=torch.bool)
+    for i, (sp, a) in enumerate(zip(specs, aux)):
+        rows, cols = sp["rows"], sp["cols"]
+        n, sl = rows * cols, slice(sp["off"], sp["off"] + rows * cols)
+        name = f"{tag}/seg{i}:{rows}x{cols}"
+        if sp["tonly"]:
+            assert same_bits(a["sh"].read(), a["src"]), name
+            assert same_bits(a["sht"].read(), layout(layout_inverse(a["src"], rows, cols, sp["sh"]),
+                                                     rows, cols, sp["sht"], True)), name
+            continue                                 # p, g, m, v: untouched, checked below
+        covered[sl] = True
+        gin = g0[sl]
+        if sp["slab"]:
+            gin = slab_sum(a["slab"], sp["slab"][1], n)
+            assert same_bits(got["g"][sl], gin), name + ": slab sum order"
+        else:
+            assert same_bits(got["g"][sl], gin), name + ": gradient overwritten"
+        if check:
+            measure(name, kind, h, step, p0[sl], gin, m0[sl], v0[sl],
+                    {k: got[k][sl] for k in ("p", "m", "v") if k in got})
+        pb = got["p"][sl].to(BF)
+        if sp["sh"]:
+            assert same_bits(a["sh"].read(), layout(pb, rows, cols, sp["sh"], False)), name + " shadow"
+        if sp["sht"]:
+            assert same_bits(a["sht"].read(), layout(pb, rows, cols, sp["sht"], True)), name + " shadow_t"
+        if sp["lo"]:
+            lo = (got["p"][sl] - pb.to(F32)).to(BF)
+            assert same_bits(a["lo"].read(), lo), name + " shadow_lo"
+    for k in got:                                    # gaps and transpose-only segments
+        assert same_bits(got[k][~covered], ins[k][~covered]), f"{tag}: {k} changed outside the segments"
+    return got
+
+
+def layout_inverse(flat, rows, cols, how):
+    """The [rows][cols] matrix whose `how` layout is `flat` (row-major bf16 tensor, 1-D)."""
+    if how != "frag":
+        return flat.clone()
+    idx = frag_major(torch.arange(rows * cols).view(rows, cols))
+    out = torch.empty_like(flat)
+    out[idx] = flat
+    return out
+
+
+# ------------------------------------------------------------------ whole arenas vs the CPU path
 def _pair(arch, kind, gpu):
     arenas = [FlatArena(get_spec(arch), d) for d in ("cpu", gpu)]
     g = torch.Generator().manual_seed(0)
@@ -27,8 +406,7 @@ def _pair(arch, kind, gpu):
 def test_optim_kernel_matches_cpu(gpu, kind, frag):
     """frag: fc1.weight's bf16 copies in the MFMA-fragment-major layouts the CNN step uses
     (kernels.h frag_pos), else row-major."""
-    from pytorch_distributed_mnist_amd.ops import _ext
-    C = _ext.require()
+    C = _C()
     (ac, ag), (oc, og) = _pair("cnn", kind, gpu)
     n = ag.spec.total
     # shadows for fc1.weight (transposed) and conv2.weight (plain)
@@ -61,9 +439,16 @@ def test_optim_kernel_matches_cpu(gpu, kind, frag):
                          False, grad_scale, segs)
     torch.cuda.synchronize()
     assert torch.allclose(ag.params.cpu(), ac.params, atol=1e-6, rtol=1e-5)
+    # the optimizer state.  exp_avg_sq: sums of positive terms, so a relative bound holds:
+    # 1.3e-5 from (1.f - float(beta2)) against torch's float(1 - beta2) (module docstring)
+    # plus a few fp32 roundings
+    if kind == "adam":
+        assert torch.allclose(og.exp_avg.cpu(), oc.exp_avg, atol=1e-6, rtol=1e-5)
+        assert torch.allclose(og.exp_avg_sq.cpu(), oc.exp_avg_sq, atol=0.0, rtol=2e-5)
+    else:
+        assert torch.allclose(og.momentum_buffer.cpu(), oc.momentum_buffer, atol=1e-6, rtol=1e-5)
     w = ag.params[off_fc1:off_fc1 + 128 * 9216]
     if frag:
-        from pytorch_distributed_mnist_amd.runtime.cnn_step import frag_major, frag_major_t
         wb = w.view(128, 9216).to(torch.bfloat16)
         assert torch.equal(sh_fc1, frag_major(wb))
         assert torch.equal(sht_fc1, frag_major_t(wb))
@@ -71,6 +456,7 @@ def test_optim_kernel_matches_cpu(gpu, kind, frag):
         assert torch.equal(sh_fc1, w.to(torch.bfloat16))
         assert torch.equal(sht_fc1.view(9216, 128), w.view(128, 9216).t().to(torch.bfloat16))
     w2 = ag.params[off_c2:off_c2 + 64 * 288]
+    assert torch.equal(sh_c2, w2.to(torch.bfloat16))
     assert torch.equal(sht_c2.view(288, 64), w2.view(64, 288).t().to(torch.bfloat16))
 
 
@@ -79,8 +465,7 @@ def test_optim_slab_segments_ragged_and_bump(gpu, kind):
     """Slab segments (the gradient is the fixed-order sum of per-workgroup slabs) with a
     numel that is not a multiple of 4 (the Linear bias: 10), and the launch's counter bump:
     same parameters as the optimizer over the pre-summed gradient."""
-    from pytorch_distributed_mnist_amd.ops import _ext
-    C = _ext.require()
+    C = _C()
     (ac, ag), (oc, og) = _pair("linear", kind, gpu)
     spec = ag.spec
     nslab, stride = 37, 7856
@@ -118,3 +503,215 @@ def test_optim_slab_segments_ragged_and_bump(gpu, kind):
         assert d < 1e-5, (name, d)
     # the arena padding after the bias (the slab's loss / correct columns) is untouched
     assert torch.equal(ag.params[ob + 10:], before[ob + 10:])
+
+
+# ------------------------------------------------------------------ a. hyper-parameter grid
+PLAIN_N = 2048 + 13       # one full chunk plus a ragged tail that reaches the scalar loop
+DATA = [(1.0, 1.0), (1e-3, 1e-3)]     # (parameter scale, gradient scale)
+
+
+@pytest.mark.parametrize("name,hyper", [
+    ("mom_wd", dict(mom=0.9, wd=1e-4)), ("plain", dict(mom=0.0, wd=0.0)),
+    ("damp", dict(mom=0.9, damp=0.1)), ("nesterov", dict(mom=0.9, nesterov=True)),
+    ("all", dict(mom=0.9, wd=1e-4, damp=0.1, nesterov=True))])
+def test_sgd_hyper_grid(gpu, name, hyper):
+    """SGD on one plain segment: grad_scale 1 and 0.25, the first step (buf = d_p, whatever
+    the buffer held) and a later one, two data scales."""
+    for gs in (1.0, 0.25):
+        for step in (1, 2):
+            for di, (ps, gsc) in enumerate(DATA):
+                run_segments(gpu, "sgd", sgd(gs=gs, **hyper), step, PLAIN_N + 24,
+                             [seg(12, 1, PLAIN_N)], seed=100 + di, pscale=ps, gscale=gsc,
+                             tag=f"plain-sgd-{name}/gs{gs}/d{di}")
+
+
+@pytest.mark.parametrize("wd", [0.0, 1e-2])
+@pytest.mark.parametrize("betas", [(0.9, 0.999), (0.8, 0.9995), (0.4, 0.999)])
+def test_adam_hyper_grid(gpu, wd, betas):
+    """Adam on one plain segment: eps 1e-8 and 1e-3; steps 1 (zero state: v is 0 where the
+    gradient is), 2 and 1000 (bias corrections from pow in double); two data scales.  betas
+    (0.4, ...) takes lerp's weight >= 0.5 branch."""
+    for eps in (1e-8, 1e-3):
+        for step in (1, 2, 1000):
+            for di, (ps, gsc) in enumerate(DATA):
+                run_segments(gpu, "adam", adam(betas=betas, eps=eps, wd=wd), step, PLAIN_N + 24,
+                             [seg(12, 1, PLAIN_N)], seed=200 + di, pscale=ps, gscale=gsc,
+                             zero_state=step == 1, tag=f"plain-adam-b{betas[0]}-wd{wd}/eps{eps}/d{di}")
+
+
+def test_measure_rejects_a_wrong_beta2(gpu):
+    """The case the allclose(atol=1e-6, rtol=1e-5) of test_optim_kernel_matches_cpu lets
+    through: the kernel run with betas (0.9, 0.9995), the reference with (0.9, 0.999)."""
+    C = _C()
+    gen = torch.Generator().manual_seed(7)
+    n = PLAIN_N
+    p0, g0 = torch.randn(n, generator=gen), torch.randn(n, generator=gen)
+    m0, v0 = torch.randn(n, generator=gen) * 0.5, torch.randn(n, generator=gen) ** 2
+    dev = [t.clone().to(gpu) for t in (p0, g0, m0, v0)]
+    launch(C, gpu, "adam", adam(betas=(0.9, 0.9995)), 3, *dev, [(0, 1, n, None, None)])
+    got = {k: t.cpu() for k, t in zip(("p", "g", "m", "v"), dev)}
+    with pytest.raises(AssertionError):
+        measure("wrong-beta2", "adam", adam(), 3, p0, g0, m0, v0, got)
+
+
+# ------------------------------------------------------------------ b. transposed-tile shapes
+TILE_CASES = [
+    # rows, cols, shadow, shadow_t
+    (32, 64, "row", "row"), (33, 65, "row", "row"), (1, 8, "row", "row"), (5, 7, "row", "row"),
+    (40, 72, "row", "row"), (64, 288, "row", "row"), (32, 64, None, "row"),
+    (32, 64, "frag", "row"), (32, 96, "frag", "row"), (64, 288, "frag", "row"),
+    (32, 64, "row", "frag"), (64, 32, "row", "frag"), (128, 9216, "frag", "frag"),
+    (16, 64, "frag", None), (48, 96, "frag", None),          # a row shard of W1
+]
+KIND_HYPER = [("sgd", sgd(mom=0.9, wd=1e-4), 2), ("adam", adam(wd=1e-2), 2)]
+
+
+@pytest.mark.parametrize("rows,cols,sh,sht", TILE_CASES)
+def test_transposed_tile_shapes(gpu, rows, cols, sh, sht):
+    """The 32 x 64 tile path: exact tiles, ragged rows / columns, rows whose first element is
+    not 16-byte aligned ((e & 3) != 0: the scalar fall-back), both fragment-major layouts,
+    a shadow_t-only segment and the shadow-only row shard."""
+    for kind, h, step in KIND_HYPER:
+        run_segments(gpu, kind, h, step, rows * cols + 28, [seg(8, rows, cols, sh, sht)],
+                     seed=rows * 131 + cols, tag=f"tile-{sh}-{sht}")
+
+
+# ------------------------------------------------------------------ c. transpose-only
+def _tonly_cases():
+    shapes = [(32, 64), (33, 65), (1, 8), (5, 7), (40, 72), (64, 288), (32, 96), (64, 32),
+              (16, 64), (48, 96), (128, 9216)]
+    out = []
+    for r, c in shapes:
+        for sf in (False, True):
+            for tf in (False, True):
+                if (sf and (r % 16 or c % 32)) or (tf and (r % 32 or c % 16)):
+                    continue                         # bind.cpp rejects these
+                out.append((r, c, "frag" if sf else "row", "frag" if tf else "row"))
+    return out
+
+
+@pytest.mark.parametrize("rows,cols,sh,sht", _tonly_cases())
+def test_transpose_only(gpu, rows, cols, sh, sht):
+    """tonly: shadow_t = transpose(shadow) in either layout; shadow, p, g, m and v (all
+    poisoned) keep their bits."""
+    kind, h, step = KIND_HYPER[(rows + cols) // 8 % 2]
+    run_segments(gpu, kind, h, step, rows * cols + 28,
+                 [seg(8, rows, cols, sh, sht, tonly=True)], seed=rows + cols, tag="tonly")
+
+
+# ------------------------------------------------------------------ d. shadow_lo
+def _halfway_patch(k):
+    """First k elements: p0, g with lr = 1, momentum 0, so that p = p0 - g is exactly a value
+    whose low 16 bits make bf16(p) (0x8000) or bf16(p - bf16(p)) (0x4040, 0x40c0) a tie."""
+    def patch(p0, g0):
+        t = torch.randn(k, generator=torch.Generator().manual_seed(k))
+        low = torch.tensor([0x8000, 0x4040, 0x40c0, 0x8000 | 0x10000], dtype=torch.int32)
+        tb = (t.view(torch.int32) & ~0x1ffff) | low[torch.arange(k) % 4]
+        t = tb.view(F32)
+        g = torch.ldexp(torch.ones(k), torch.frexp(t.abs())[1] - 8)     # one bf16 ulp of t
+        p = t + g
+        assert torch.equal(p.double(), t.double() + g.double())          # exact
+        assert torch.equal(p - g, t)
+        p0[:k], g0[:k] = p, g
+        patch.target = t
+    return patch
+
+
+@pytest.mark.parametrize("rows,cols", [(64, 288), (1, 2048 + 6)])
+def test_shadow_lo(gpu, rows, cols):
+    """The fp32 program's split-bf16 copies on plain segments (vector chunk and scalar tail),
+    with weights landing on bf16 half-way points; then ordinary SGD and Adam updates."""
+    n = rows * cols
+    patch = _halfway_patch(512)
+
+    def at_segment(p0, g0):
+        patch(p0[8:], g0[8:])
+    got = run_segments(gpu, "sgd", sgd(lr=1.0), 2, n + 28, [seg(8, rows, cols, "row", None, lo=True)],
+                       seed=5, patch=at_segment, tag="lo-halfway")
+    assert same_bits(got["p"][8:8 + 512], patch.target)
+    for kind, h, step in KIND_HYPER:
+        run_segments(gpu, kind, h, step, n + 28, [seg(8, rows, cols, "row", None, lo=True)],
+                     seed=6, tag="lo")
+
+
+# ------------------------------------------------------------------ e. slab segments
+SLAB_PAIRS = [(4, 1), (4, 129), (10, 15), (10, 256), (64, 16), (64, 192), (65, 17), (65, 128),
+              (65, 129), (18432, 1), (18432, 17)]
+
+
+@pytest.mark.parametrize("numel,nslab", SLAB_PAIRS)
+def test_slab_segments(gpu, numel, nslab):
+    """Slab-reduced segments: the written gradient is bit-equal to the documented order (a
+    second pass of the j0 loop above 128 slabs, empty groups below 16), slab_col0 != 0, a
+    stride larger than needed, NaN in every slab column of other segments."""
+    col0 = 8
+    stride = col0 + (numel + 3) // 4 * 4 + 12
+    for kind, h, step in KIND_HYPER:
+        run_segments(gpu, kind, h, step, numel + 28, [seg(12, 1, numel, slab=(nslab, col0, stride))],
+                     seed=numel + nslab, tag=f"slab-{numel}x{nslab}")
+
+
+@pytest.mark.parametrize("sh,sht,lo,nslab", [("frag", "row", False, 16), ("row", None, True, 15)])
+def test_slab_segments_with_shadows(gpu, sh, sht, lo, nslab):
+    """conv2.weight as the steps run it at world size 1: slab + fragment-major shadow +
+    row-major shadow_t (bf16 program), slab + shadow + shadow_lo (fp32 program)."""
+    for kind, h, step in KIND_HYPER:
+        run_segments(gpu, kind, h, step, 18432 + 28,
+                     [seg(12, 64, 288, sh, sht, lo=lo, slab=(nslab, 4, 18432 + 4 + 380))],
+                     seed=nslab, tag=f"slab-conv2-{sh}-{sht}-lo{int(lo)}")
+
+
+def test_slab_metrics_workgroup(gpu):
+    """metrics=(slab, nslab, col, stride, out): the extra last workgroup adds the fp64 sums of
+    two slab columns and does not shift the segment search: p, g, m are bit-identical to the
+    same launch without it."""
+    gen = torch.Generator().manual_seed(11)
+    mnslab, mcol, mstride = 200, 3, 8
+    mslab = torch.randn(mnslab, mstride, generator=gen)
+    specs = [seg(12, 1, 65, slab=(129, 8, 92)), seg(96, 1, PLAIN_N), seg(96 + PLAIN_N + 7, 33, 65, "row", "row")]
+    total = 96 + PLAIN_N + 7 + 33 * 65 + 9
+    kind, h, step = KIND_HYPER[0]
+    init = torch.tensor([1.5, -2.5, 7.0], dtype=F64)
+    out = init.clone().to(gpu)
+    a = run_segments(gpu, kind, h, step, total, specs, seed=12, tag="metrics-on",
+                     metrics=(mslab.reshape(-1).to(gpu), mnslab, mcol, mstride, out))
+    b = run_segments(gpu, kind, h, step, total, specs, seed=12, tag="metrics-off", check=False)
+    for k in a:
+        assert same_bits(a[k], b[k]), k
+    got = out.cpu()
+    for j in range(2):
+        col = mslab[:, mcol + j].double()
+        assert abs(got[j] - (init[j] + col.sum())) <= 1e-12 * (abs(init[j]) + col.abs().sum())
+    assert got[2] == init[2]                         # the sample count is another kernel's
+
+
+# ------------------------------------------------------------------ f. segment table
+def _table_specs():
+    specs, off = [], 4
+    for s in (seg(0, 1, 65, slab=(17, 4, 80)), seg(0, 1, PLAIN_N), seg(0, 33, 65, "row", "row"),
+              seg(0, 32, 64, "row", "frag", tonly=True), seg(0, 64, 288, "row", None, lo=True),
+              seg(0, 64, 288, "frag", "row", slab=(16, 0, 18432)), seg(0, 32, 96, "frag", "row"),
+              seg(0, 1, 7)):
+        s["off"] = off
+        specs.append(s)
+        off += (s["rows"] * s["cols"] + 3) // 4 * 4 + 8          # a gap after every segment
+    return specs, off
+
+
+@pytest.mark.parametrize("kind,h,step", KIND_HYPER)
+def test_segment_table_of_eight(gpu, kind, h, step):
+    """One launch with OPT_MAX_SEG segments of every kind and gaps between them: every
+    segment is right and every gap keeps its bits."""
+    specs, total = _table_specs()
+    assert len(specs) == 8
+    run_segments(gpu, kind, h, step, total, specs, seed=21, tag="table8")
+
+
+def test_nine_segments_are_rejected(gpu):
+    C = _C()
+    z = torch.zeros(64, device=gpu)
+    segs = [(4 * i, 1, 4, None, None) for i in range(9)]
+    before = z.clone()
+    with pytest.raises(RuntimeError, match="optimizer segments"):
+        launch(C, gpu, "sgd", sgd(), 1, z, z.clone(), z.clone(), None, segs)
+    assert torch.equal(z, before)

@@ -808,7 +808,7 @@ void conv_reduce(at::Tensor slab, int64_t nblk, at::Tensor gw2, at::Tensor gb2, 
 
 int64_t cnn_bwd_nblk(int64_t B, int64_t ipb, int64_t bands) { return conv_blocks(B, ipb, bands); }
 
-// ------------------------------------------------------------------ CNN fp32 (cnn_f32.hip)
+// ------------------------------------------------------------------ CNN fp32 (cnn_f32x3.hip, cnn_f32_exact.hip)
 // the split-bf16 W2^T planes the x3 forward writes for the x3 backward (2 x 36864 B)
 static float* w2x_ptr(const c10::optional<at::Tensor>& w2x) {
   TORCH_CHECK(w2x.has_value() && w2x->defined(), "the split-bf16 path needs the w2x buffer");
@@ -940,6 +940,8 @@ at::Tensor read_stamps(const std::string& which) {
   at::Tensor t = at::zeros({256, 16}, at::TensorOptions().dtype(at::kLong));
   auto* p = reinterpret_cast<unsigned long long*>(t.data_ptr<int64_t>());
   if (which == "fwd") read_stamps_fwd(p);
+  else if (which == "head") read_stamps_head(p);
+  else if (which == "fc1_bwd") read_stamps_fc1_bwd(p);
   else if (which == "fwd_band") read_stamps_fwd_band(p);
   else if (which == "bwd_band") read_stamps_bwd_band(p);
   else if (which == "f32") read_stamps_f32(p);

@@ -234,7 +234,7 @@ void launch_cnn_bwd_band(const __bf16* a1g, const __bf16* xng, const __bf16* dpo
 void launch_conv_reduce(const float* slab, int nblk, float* gw2, float* gb2, float* gw1, float* gb1,
                         hipStream_t st);
 
-// ---------------------------------------------------------------- CNN (fp32, cnn_f32.hip)
+// ---------------------------------------------------------------- CNN (fp32, cnn_f32x3.hip / cnn_f32_exact.hip)
 // The reference's precision on the fp32 MFMA (v_mfma_f32_16x16x4_f32).  fp32 layouts as the
 // bf16 path (pool [B][12*12][64], pmask, conv2 weight [co][tap][ci], fc1 weight [128][9216]);
 // w2s: conv2's weight as split-bf16 hi / lo planes [2][64][288] (split-bf16 path only).
@@ -267,8 +267,11 @@ void launch_lin_predict(const uint8_t* images, const int32_t* labels, int n_tota
                         const float* b, float* logp, int32_t* pred, int64_t* confusion,
                         double* metrics, hipStream_t st);
 
-// diagnostic timestamps (all zero unless built with PDM_STAMPS=1)
+// diagnostic timestamps (all zero unless built with PDM_STAMPS=1); one buffer per kernel file
+// (cnn_common.h PDM_STAMP_READER)
 void read_stamps_fwd(unsigned long long* host);
+void read_stamps_head(unsigned long long* host);
+void read_stamps_fc1_bwd(unsigned long long* host);
 void read_stamps_bwd(unsigned long long* host);
 void read_stamps_fwd_band(unsigned long long* host);
 void read_stamps_bwd_band(unsigned long long* host);

@@ -457,12 +457,4 @@ void launch_cnn_bwd_band(const __bf16* a1g, const __bf16* xng, const __bf16* dpo
   }
 }
 
-#ifdef PDM_STAMPS
-void read_stamps_bwd_band(unsigned long long* host) {
-  hipMemcpyFromSymbol(host, HIP_SYMBOL(pdm_stamps), sizeof(unsigned long long) * 256 * 16);
-}
-#else
-void read_stamps_bwd_band(unsigned long long* host) {
-  for (int i = 0; i < 256 * 16; ++i) host[i] = 0;
-}
-#endif
+PDM_STAMP_READER(bwd_band)

@@ -8,8 +8,14 @@
 
 // Diagnostic build only (PDM_STAMPS=1 python -m pytorch_distributed_mnist_amd.build):
 // thread 0 of blocks 0..255 records s_memtime at phase boundaries; never in a timed build.
+// Every translation unit has its own buffer; PDM_STAMP_READER(name) defines its host reader
+// read_stamps_<name> (kernels.h; zeros in a build without stamps).
 #ifdef PDM_STAMPS
 static __device__ unsigned long long pdm_stamps[256 * 16];
+#define PDM_STAMP_READER(name)                                                               \
+  void read_stamps_##name(unsigned long long* host) {                                        \
+    hipMemcpyFromSymbol(host, HIP_SYMBOL(pdm_stamps), sizeof(unsigned long long) * 256 * 16); \
+  }
 #define PDM_STAMP(slot)                                                              \
   do {                                                                               \
     if (threadIdx.x == 0 && blockIdx.x < 256)                                        \
@@ -21,6 +27,10 @@ static __device__ unsigned long long pdm_stamps[256 * 16];
     if (blockIdx.x < 256) pdm_stamps[blockIdx.x * 16 + (slot)] = (val);              \
   } while (0)
 #else
+#define PDM_STAMP_READER(name)                        \
+  void read_stamps_##name(unsigned long long* host) { \
+    for (int i = 0; i < 256 * 16; ++i) host[i] = 0;   \
+  }
 #define PDM_STAMP(slot) \
   do {                  \
   } while (0)

@@ -303,12 +303,4 @@ void launch_cnn_fwd_band(const uint8_t* images, const int32_t* labels, const int
   }
 }
 
-#ifdef PDM_STAMPS
-void read_stamps_fwd_band(unsigned long long* host) {
-  hipMemcpyFromSymbol(host, HIP_SYMBOL(pdm_stamps), sizeof(unsigned long long) * 256 * 16);
-}
-#else
-void read_stamps_fwd_band(unsigned long long* host) {
-  for (int i = 0; i < 256 * 16; ++i) host[i] = 0;
-}
-#endif
+PDM_STAMP_READER(fwd_band)

@@ -1,5 +1,5 @@
 // Optimizer math shared by the optimizer kernel (optim.hip) and the world-size-1 fc1 update
-// fused into cnn_bwd (cnn_bwd.hip): torch's single-tensor Adam / SGD op order, fp32.
+// fused into fc1_bwd (fc1_bwd.hip): torch's single-tensor Adam / SGD op order, fp32.
 #pragma once
 #include "../common.h"
 #include "../kernels.h"

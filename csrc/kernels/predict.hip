@@ -1,5 +1,5 @@
 // Prediction heads: the inference twins of the evaluation heads (cnn_head<eval> in
-// cnn_fwd.hip, lin_eval in linear.hip).  Where those fold a row's logits into three fp64 sums,
+// cnn_head.hip, lin_eval in linear.hip).  Where those fold a row's logits into three fp64 sums,
 // these write what the model said about every row:
 //   logp      fp32  [B][10]   log-softmax of the logits
 //   pred      int32 [B]       first maximum (torch.argmax; row_xent's `correct` rule)

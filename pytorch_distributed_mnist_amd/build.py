@@ -15,7 +15,6 @@ from __future__ import annotations
 import argparse
 import glob
 import hashlib
-import re
 import os
 import subprocess
 import sys
@@ -74,10 +73,9 @@ def compile_flags(abi: int, inc):
     return flags
 
 
-# Per-file compiler flags.  fc1_fwd / fc1_bwd are translation units of their own (wrappers
-# that include cnn_fwd.hip / cnn_bwd.hip with a section switch) so that they can use the
-# max-ilp machine scheduler, which measured faster for them and slower for cnn_fwd /
-# cnn_bwd (docs/kernels.md, tools/gpu_ab.sh).
+# Per-file compiler flags.  fc1_fwd, fc1_bwd and cnn_head are kernels in files of their own,
+# so each can use the machine scheduler that measured faster for it (and slower for cnn_fwd /
+# cnn_bwd; docs/kernels.md, tools/gpu_ab.sh).
 FILE_FLAGS = {
     "kernels/fc1_fwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "kernels/fc1_bwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
@@ -95,22 +93,10 @@ def file_flags():
     return ff
 
 
-def _included_sources(path):
-    """.hip files a wrapper source #includes (their text is part of its object's hash)."""
-    out = []
-    with open(path) as f:
-        for line in f:
-            m = re.match(r'\s*#include\s+"([^"]+\.hip)"', line)
-            if m:
-                out.append(os.path.join(os.path.dirname(path), m.group(1)))
-    return out
-
-
 def _hash(path, flags, hdr_digest):
     h = hashlib.sha256()
-    for p in [path] + _included_sources(path):
-        with open(p, "rb") as f:
-            h.update(f.read())
+    with open(path, "rb") as f:
+        h.update(f.read())
     h.update(" ".join(flags).encode())
     h.update(hdr_digest)
     return h.hexdigest()[:20]

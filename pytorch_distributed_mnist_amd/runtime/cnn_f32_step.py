@@ -2,7 +2,7 @@
 
 The reference trains in fp32 (``multi_proc_single_gpu.py:185-191``).  Same chain as the bf16
 program (``cnn_step.py``) with fp32 activations, gradients and weights
-(``csrc/kernels/cnn_f32.hip``).  The conv2 and fc1 GEMMs run as split-bf16 products on the
+(``csrc/kernels/cnn_f32x3.hip``, ``cnn_f32_exact.hip``).  The conv2 and fc1 GEMMs run as split-bf16 products on the
 bf16 MFMA (``conv_x3``, see below) or exactly on the fp32 MFMA (``v_mfma_f32_16x16x4_f32``):
 
   f32_fwd      gather-free epoch buffer row, normalise, conv1 + ReLU, conv2 + ReLU + maxpool
@@ -91,7 +91,7 @@ class CnnStepF32(GpuStepBase):
         self.G = {n: a.grad(n) for n in self.P}
         self.fuse_conv_reduce = not self.reducer.active
         # conv2 and fc1 products (the step's FLOPs): "x3" (default) = split-bf16 on the bf16 MFMA
-        # (hi.hi + hi.lo + lo.hi, fp32 accumulation; cnn_f32.hip f32x3_*): 4.5e-6 relative
+        # (hi.hi + hi.lo + lo.hi, fp32 accumulation; cnn_f32x3.hip): 4.5e-6 relative
         # error on a conv2 output against fp64, where exact fp32 gives 1.6e-7 and TF32 --
         # cuDNN's default for fp32 convolutions -- 2.9e-4 (tests/test_split_bf16.py); the
         # step's gradients stay within 1e-4 of fp64 (tests/test_gpu_cnn_f32.py).

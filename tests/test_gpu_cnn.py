@@ -60,7 +60,7 @@ class _RoundGrad(torch.autograd.Function):
 
 def bf16_mirrored_forward(p, x):
     """The CNN forward with the kernel chain's bf16 rounding points (csrc/kernels/cnn_fwd.hip,
-    cnn_bwd.hip, docs/kernels.md): x, conv1 / conv2 / fc1 weights, a1 and the pooled features
+    fc1_fwd.hip, cnn_head.hip, fc1_bwd.hip, cnn_bwd.hip, docs/kernels.md): x, conv1 / conv2 / fc1 weights, a1 and the pooled features
     are bf16 operands; dh (fc1 pre-activation grad, stored bf16 by cnn_head), dpool (bf16
     from fc1_bwd's dX tiles) and da1 (the conv2 dgrad after relu', the bf16 A operand of the
     conv1 weight-gradient MFMA) are rounded in the backward.  fp32 everywhere else."""

@@ -1,4 +1,4 @@
-"""CNN fp32 GPU path (``--dtype fp32``, cnn_f32.hip on v_mfma_f32_16x16x4_f32) against fp32
+"""CNN fp32 GPU path (``--dtype fp32``, cnn_f32_exact.hip on v_mfma_f32_16x16x4_f32) against fp32
 PyTorch autograd: the reference trains in fp32 (multi_proc_single_gpu.py:185-191), so the
 gradients of one step must agree to fp32 summation-order noise (<= 1e-4 relative)."""
 import pytest

@@ -1,4 +1,4 @@
-"""The fp32 program's kernels (csrc/kernels/cnn_f32.hip) called one by one on synthetic tensors,
+"""The fp32 program's kernels (csrc/kernels/cnn_f32x3.hip, cnn_f32_exact.hip) called one by one on synthetic tensors,
 every output element by element against an fp64 reference computed on the CPU from the very
 operands the kernel read, in both product modes (x3 = split-bf16 on the bf16 MFMA, exact = the
 fp32 MFMA):

@@ -1,4 +1,4 @@
-"""cnn_head (head_body in csrc/kernels/cnn_fwd.hip) called directly on synthetic inputs, every
+"""cnn_head (head_body in csrc/kernels/cnn_head.hip) called directly on synthetic inputs, every
 output against an fp64 reference written in plain torch.
 
 The head reduces fc1's split-K partials, applies bias + ReLU, fc2, log-softmax / NLL and

@@ -2,7 +2,7 @@
 
 The formula of ``optim_common.h update<OPT_SGD>`` runs in three kernels: ``optim_kernel``'s
 transposed-shadow tile (tests/test_gpu_optim.py), ``fc1_bwd``'s dW epilogue (``fc_update``,
-cnn_bwd.hip) and the extra workgroups of the forward launch (``fc_carry``, fc_carry.h).
+fc1_bwd.hip) and the extra workgroups of the forward launch (``fc_carry``, fc_carry.h).
 test_gpu_comm.py shows them bit-identical to each other inside whole steps; here each is
 pinned on its own to ``ref_update`` (test_gpu_optim.py: fp64 on the fp32 inputs the kernel
 read, condition-scaled error, within 8 x ``FlatSGD.step_cpu`` and within R * 2^-23), its bf16

@@ -1,5 +1,5 @@
 """Precision of the split-bf16 ("bf16x3") products the fp32 CNN path runs its conv2 GEMMs with
-(csrc/kernels/cnn_f32.hip f32x3_*): x = hi + lo with hi = bf16(x), lo = bf16(x - hi), and a
+(csrc/kernels/cnn_f32x3.hip): x = hi + lo with hi = bf16(x), lo = bf16(x - hi), and a
 product taken as hi.hi + hi.lo + lo.hi with fp32 accumulation.  Emulated here in torch on the
 CPU (bf16 products are exact in fp32) against fp64, next to TF32 (10-bit mantissa operands,
 what cuDNN uses for fp32 convolutions by default) and plain bf16 operands."""

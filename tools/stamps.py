@@ -33,17 +33,17 @@ for which, names in (("fwd", ["start", "gathered(barrier)", "conv1(barrier)", "c
     print("   block start skew (cycles):", (st[:, 0] - t0).max().item(),
           " last end:", (st[:, n - 1] - t0).max().item())
     if which == "fwd" and B <= 256:
-        hs = st[:B // 4, 10:16]            # cnn_head, blocks 0 .. B/4 - 1 (one row group each)
+        # cnn_head, blocks 0 .. B/4 - 1 (one row group each), slots 10-15 of its own buffer
+        hs = C.read_stamps("head").double()[:B // 4, 10:16]
         hb = hs[:, 0:1]
         hm = (hs - hb).median(dim=0).values
         print("   head: partials summed / xent / dh stored / slab acc / end (rel, median):",
               " ".join(f"{v:.0f}" for v in hm[1:].tolist()))
-    if which == "fwd" and B > 64:
-        ws = st[64:min(B, 256), 10:16] - st[64:min(B, 256), 0:1]
+    if which == "fwd":
+        ws = st[:min(B, 256), 10:16] - st[:min(B, 256), 0:1]
         print("   conv2 end per wave 1..6 (rel, median):",
               " ".join(f"{v:.0f}" for v in ws.median(dim=0).values.tolist()),
-              " wave 0:", f"{(st[64:min(B, 256), 3] - st[64:min(B, 256), 0]).median().item():.0f}")
-    if which == "fwd":
+              " wave 0:", f"{(st[:min(B, 256), 3] - st[:min(B, 256), 0]).median().item():.0f}")
         print("   image load issued (rel)", (st[:, 8] - st[:, 0]).median().item(),
               " image landed (rel)", (st[:, 9] - st[:, 0]).median().item())
     if which == "bwd":

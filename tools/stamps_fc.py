@@ -20,14 +20,8 @@ st = p.gpu
 for _ in range(5):
     st.train_step(B)
 torch.cuda.synchronize()
-C, G = st.C, st.G
 ldt = -(-B // 32) * 32
-for _ in range(3):   # fc1_bwd alone (cnn_bwd would overwrite the stamps)
-    C.fc1_bwd(st.dh, st.dht, ldt, st.pool, st.current_wf1t(), B, G["fc1.weight"], st.dpool, st.head_slab,
-              G["fc2.weight"], G["fc2.bias"], G["fc1.bias"], st.metrics.train_view(),
-              st._fc_update() if st.fuse_fc1 else None)
-torch.cuda.synchronize()
-s = C.read_stamps("bwd").double().view(256, 16)
+s = st.C.read_stamps("fc1_bwd").double().view(256, 16)   # the last step's fc1_bwd
 ndx = ldt // 32 * 24
 dx = s[:min(ndx, 256), 0:4]
 dw = s[:144, 8:14]

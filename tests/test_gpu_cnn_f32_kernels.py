@@ -159,8 +159,9 @@ def written(buf, n, name):
     return buf[:n]
 
 
-def elementwise(tag, got, ref, s, emu, K, x3, margin=MARGIN):
-    """The module docstring's check of one output."""
+def elementwise(tag, got, ref, s, emu, K, x3, margin=MARGIN, floor=0.0):
+    """The module docstring's check of one output.  floor: the least e_ref the comparison
+    uses (tests/test_gpu_cnn_bf16_kernels.py: sums of bare bf16 values)."""
     got, emu = got.double(), emu.double()
     assert got.shape == ref.shape == s.shape == emu.shape, tag
     zero = s == 0
@@ -174,12 +175,60 @@ def elementwise(tag, got, ref, s, emu, K, x3, margin=MARGIN):
     e_r = ((emu - ref).abs()[nz] / s[nz]).max().item()
     print(f"f32k {tag}: e_kernel {e_k:.2e} e_ref {e_r:.2e} cap {cap:.2e}")
     assert e_k <= cap, (tag, e_k, cap)
-    assert e_k <= margin * e_r, (tag, e_k, e_r)
+    assert e_k <= margin * max(e_r, floor), (tag, e_k, e_r)
 
 
 def nchw_w2(w2):
     """[co][tap][ci] -> [co][ci][ky][kx]."""
     return w2.view(C2, 3, 3, C1).permute(0, 3, 1, 2).contiguous()
+
+
+def windows(z):
+    """[B, C, 24, 24] -> [B, C, 12, 12, 4], window position s = 2 dy + dx."""
+    B = z.shape[0]
+    return z.view(B, -1, 12, 2, 12, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, -1, 12, 12, 4)
+
+
+def nhwc(t):
+    """[B, 64, 12, 12] -> the kernels' [B][pp][co]."""
+    return t.permute(0, 2, 3, 1).reshape(t.shape[0], FEAT)
+
+
+def window_ties(a1n, z2):
+    """The module docstring's max-pool tie rule.  a1n [B, 32, 26, 26]: the a1 conv2 read; z2
+    [B, 64, 24, 24]: its fp64 conv2.  Returns, per window [B, 64, 12, 12]: the fp64 maximum, its
+    lead over the positions that are not copies of it, the expected argmax position (the first
+    copy of the maximum) and whether the maximum has copies."""
+    B = a1n.shape[0]
+    win = windows(z2)
+    m64, arg64 = win.max(-1)
+    # window positions whose 3x3x32 a1 patches are bit-identical hold the same conv2 value in
+    # the kernel (the same arithmetic on the same numbers): the first of them stands for all
+    patches = windows(F.unfold(a1n, 3).view(B, 288, 24, 24))
+    eq = (patches.unsqueeze(-1) == patches.unsqueeze(-2)).all(1)        # [B, 12, 12, 4 i, 4 j]
+    pos4 = torch.arange(4).view(4, 1)
+    first = torch.where(eq, pos4, 4).min(-2).values                     # [B, 12, 12, 4 j]
+    eq_c = eq.unsqueeze(1).expand(B, C2, 12, 12, 4, 4)
+    like = eq_c.gather(4, arg64[..., None, None].expand(B, C2, 12, 12, 1, 4)).squeeze(4)
+    want = first.unsqueeze(1).expand(B, C2, 12, 12, 4).gather(4, arg64.unsqueeze(-1)).squeeze(-1)
+    # the fp64 maximum's lead over the positions that are not copies of it
+    gap = m64 - win.masked_fill(like, float("-inf")).max(-1).values
+    return m64, gap, want, like.sum(-1) > 1
+
+
+def check_pmask(pmask, pool, m_k, gap_k, want_k):
+    """pmask [B, 9216] against window_ties' maximum, lead and expected position (all in the
+    kernels' [B][pp][co] order) and against the pooled values of the same launch."""
+    mk = pmask.long()
+    low = mk & 0x7f
+    ok = (mk == 0) | (((mk & 0x80) != 0) & (low != 0) & (low < 16) & ((low & (low - 1)) == 0))
+    assert ok.all(), mk[~ok][:8].tolist()
+    assert (mk[m_k <= -DELTA] == 0).all()
+    assert (mk[m_k >= DELTA] != 0).all()
+    assert ((mk != 0) == (pool > 0)).all()                              # mask and pool agree
+    sel = (mk != 0) & (gap_k > DELTA)
+    bad = sel & (low != (1 << want_k))
+    assert not bad.any(), ("argmax bit", int(bad.sum()), low[bad][:8].tolist(), want_k[bad][:8].tolist())
 
 
 # ---------------------------------------------------------------- 1. f32_fwd
@@ -325,23 +374,7 @@ def test_f32_fwd(gpu, mode, B, arg, x3):
     else:
         z2_emu = F.conv2d(a1k_n, nchw_w2(w2), b2)
 
-    def windows(z):      # [B, C, 24, 24] -> [B, C, 12, 12, 4], position s = 2 dy + dx
-        return z.view(B, -1, 12, 2, 12, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, -1, 12, 12, 4)
-
-    win = windows(z2)
-    m64, arg64 = win.max(-1)
-    # window positions whose 3x3x32 a1 patches are bit-identical hold the same conv2 value in
-    # the kernel (the same arithmetic on the same numbers): the first of them stands for all
-    patches = windows(F.unfold(a1k_n, 3).view(B, 288, 24, 24))
-    eq = (patches.unsqueeze(-1) == patches.unsqueeze(-2)).all(1)        # [B, 12, 12, 4 i, 4 j]
-    pos4 = torch.arange(4).view(4, 1)
-    first = torch.where(eq, pos4, 4).min(-2).values                     # [B, 12, 12, 4 j]
-    eq_c = eq.unsqueeze(1).expand(B, C2, 12, 12, 4, 4)
-    like = eq_c.gather(4, arg64[..., None, None].expand(B, C2, 12, 12, 1, 4)).squeeze(4)
-    want = first.unsqueeze(1).expand(B, C2, 12, 12, 4).gather(4, arg64.unsqueeze(-1)).squeeze(-1)
-    # the fp64 maximum's lead over the positions that are not copies of it
-    gap = m64 - win.masked_fill(like, float("-inf")).max(-1).values
-    tied = like.sum(-1) > 1
+    m64, gap, want, tied = window_ties(a1k_n, z2)
     # left out of the pmask comparison, from the reference alone
     near = (m64.abs() < DELTA) | (gap <= DELTA)
     share = near.double().mean().item()
@@ -351,26 +384,13 @@ def test_f32_fwd(gpu, mode, B, arg, x3):
     assert share <= 0.01, share
     assert 0.05 <= nonpos <= 0.95, nonpos
 
-    def nhwc(t):         # [B, 64, 12, 12] -> the kernels' [B][pp][co]
-        return t.permute(0, 2, 3, 1).reshape(B, FEAT)
-
     pool = written(tr["pool"], B * FEAT, "pool").view(B, FEAT)
     elementwise(f"{tag} pool", pool, nhwc(torch.relu(m64)), nhwc(windows(s2).max(-1).values),
                 nhwc(torch.relu(windows(z2_emu).max(-1).values)), 288, x3)
 
     # pmask
     assert (tr["pmask"][B * FEAT:] == 0x55).all(), "pmask written past the contract"
-    mk = tr["pmask"][:B * FEAT].view(B, FEAT).long()
-    low = mk & 0x7f
-    ok = (mk == 0) | (((mk & 0x80) != 0) & (low != 0) & (low < 16) & ((low & (low - 1)) == 0))
-    assert ok.all(), mk[~ok][:8].tolist()
-    m_k, gap_k, want_k = nhwc(m64), nhwc(gap), nhwc(want)
-    assert (mk[m_k <= -DELTA] == 0).all()
-    assert (mk[m_k >= DELTA] != 0).all()
-    assert ((mk != 0) == (pool > 0)).all()                              # mask and pool agree
-    sel = (mk != 0) & (gap_k > DELTA)
-    bad = sel & (low != (1 << want_k))
-    assert not bad.any(), ("argmax bit", int(bad.sum()), low[bad][:8].tolist(), want_k[bad][:8].tolist())
+    check_pmask(tr["pmask"][:B * FEAT].view(B, FEAT), pool, nhwc(m64), nhwc(gap), nhwc(want))
 
     # evaluation template
     assert torch.equal(ev["ylab"], tr["ylab"])
@@ -488,6 +508,13 @@ CONV_BWD = ([(B, per, False) for (B, per) in ((1, 1), (3, 1), (5, 2), (7, 3))]
             + [(B, per, True) for (B, per) in ((1, 1), (1, 6), (3, 4), (5, 7), (2, 12), (3, 100))])
 
 
+def seam_rows():
+    """The seam probe's pooled rows and a1 rows (module docstring)."""
+    prow = sorted({0, 11} | {2 * k - 1 for k in range(1, 6)} | {2 * k for k in range(1, 6)})
+    arow = sorted({0, 1, 24, 25} | {4 * k + d for k in range(1, 6) for d in (-2, -1, 0, 1)})
+    return prow, arow
+
+
 def conv_bwd_inputs(B, seam):
     g = torch.Generator().manual_seed(50 + B + (1000 if seam else 0))
     a1 = torch.relu(torch.randn(B, P1, C1, generator=g))      # about half exact zeros
@@ -498,8 +525,7 @@ def conv_bwd_inputs(B, seam):
     pmask = torch.where(pos, 0x80 | (1 << sidx), 0).to(torch.uint8)
     w2 = torch.randn(C2, 9, C1, generator=g) * (2.0 / 288) ** 0.5
     if seam:
-        prow = sorted({0, 11} | {2 * k - 1 for k in range(1, 6)} | {2 * k for k in range(1, 6)})
-        arow = sorted({0, 1, 24, 25} | {4 * k + d for k in range(1, 6) for d in (-2, -1, 0, 1)})
+        prow, arow = seam_rows()
         keep = torch.zeros(12, dtype=torch.bool)
         keep[prow] = True
         dpool = dpool.view(B, 12, 12, C2) * keep.view(1, 12, 1, 1)

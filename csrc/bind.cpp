@@ -219,6 +219,65 @@ void gather_epoch(at::Tensor images, at::Tensor labels, at::Tensor idx, at::Tens
                       cur_stream(images));
 }
 
+// gather_epoch with the train-time augmentation (kernels/augment.hip): the same arguments and
+// contract, plus the Q14 tables cosq / sinq (int32 [1024]) and invz (int32 [64]) on the device,
+// the shift range in pixels (0..8), the epoch and the 64-bit augmentation seed.
+void gather_epoch_augment(at::Tensor images, at::Tensor labels, at::Tensor idx,
+                          at::Tensor out_images, at::Tensor out_labels,
+                          c10::optional<at::Tensor> ctr, c10::optional<at::Tensor> step,
+                          int64_t step_value, int64_t max_wgs, at::Tensor cosq, at::Tensor sinq,
+                          at::Tensor invz, int64_t shift, int64_t epoch, uint64_t seed) {
+  c10::DeviceGuard g(images.device());
+  need(images, at::kByte, "images");
+  need(labels, at::kInt, "labels");
+  need(out_images, at::kByte, "out_images");
+  need(out_labels, at::kInt, "out_labels");
+  need(cosq, at::kInt, "cosq");
+  need(sinq, at::kInt, "sinq");
+  need(invz, at::kInt, "invz");
+  need_numel(cosq, 1024, "cosq");
+  need_numel(sinq, 1024, "sinq");
+  need_numel(invz, 64, "invz");
+  TORCH_CHECK(shift >= 0 && shift <= 8, "shift must be in 0..8, got ", shift);
+  TORCH_CHECK(epoch >= 0 && epoch <= 0xffffffffLL, "epoch must fit 32 bits, got ", epoch);
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.is_contiguous(), "idx must be contiguous int32");
+  const int32_t* ip = nullptr;
+  if (idx.is_cuda()) {
+    ip = idx.data_ptr<int32_t>();
+  } else {
+    TORCH_CHECK(idx.is_pinned(), "a host idx must be pinned (device-mapped) memory");
+    void* dp = nullptr;
+    const hipError_t e = hipHostGetDevicePointer(&dp, idx.data_ptr(), 0);
+    TORCH_CHECK(e == hipSuccess && dp != nullptr, "hipHostGetDevicePointer: ", hipGetErrorString(e));
+    ip = static_cast<const int32_t*>(dp);
+  }
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == 784, "images must be [N, 784]");
+  TORCH_CHECK(images.size(0) >= 1 && labels.numel() == images.size(0), "labels must be [N >= 1]");
+  const int64_t n = idx.numel();
+  TORCH_CHECK(out_images.numel() >= n * 784 && out_labels.numel() >= n, "output too small");
+  need_aligned(images.data_ptr(), 16, "images");
+  need_aligned(out_images.data_ptr(), 16, "out_images");
+  int64_t* cp = nullptr;
+  int nctr = 0;
+  if (ctr.has_value() && ctr->defined()) {
+    need(*ctr, at::kLong, "ctr");
+    TORCH_CHECK(ctr->numel() <= 256, "ctr: at most 256 counters");
+    cp = ptr<int64_t>(*ctr);
+    nctr = (int)ctr->numel();
+  }
+  int64_t* sp = nullptr;
+  if (step.has_value() && step->defined()) {
+    need(*step, at::kLong, "step");
+    sp = ptr<int64_t>(*step);
+  }
+  launch_gather_epoch_augment(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), ip, (int)n,
+                              (int)images.size(0), out_images.data_ptr<uint8_t>(),
+                              out_labels.data_ptr<int32_t>(), cp, nctr, sp, step_value,
+                              (int)max_wgs, cosq.data_ptr<int32_t>(), sinq.data_ptr<int32_t>(),
+                              invz.data_ptr<int32_t>(), (int)shift, (uint32_t)epoch, seed,
+                              cur_stream(images));
+}
+
 // ------------------------------------------------------------------ optimizer
 // segs: list of (offset, rows, cols, shadow or None, shadow_t or None
 //                [, (slab, nslab, col0, stride) or None])
@@ -982,6 +1041,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("gather_epoch", &gather_epoch, py::arg("images"), py::arg("labels"), py::arg("idx"),
         py::arg("out_images"), py::arg("out_labels"), py::arg("ctr") = py::none(),
         py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0);
+  m.def("gather_epoch_augment", &gather_epoch_augment, py::arg("images"), py::arg("labels"),
+        py::arg("idx"), py::arg("out_images"), py::arg("out_labels"), py::arg("ctr") = py::none(),
+        py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0,
+        py::arg("cosq"), py::arg("sinq"), py::arg("invz"), py::arg("shift"), py::arg("epoch"),
+        py::arg("seed"));
   m.def("xgmi_wait", &xgmi_wait);
   m.def("debug_spin", &debug_spin, py::arg("seconds"));
   m.attr("CNN_HEAD_ROWS") = CNN_HEAD_ROWS;

@@ -50,6 +50,16 @@ void launch_lin_eval(const uint8_t* images, const int32_t* labels, int n_total, 
 void launch_gather_epoch(const uint8_t* images, const int32_t* labels, const int32_t* idx, int n,
                          int nimg, uint8_t* out_images, int32_t* out_labels, int64_t* ctr,
                          int nctr, int64_t* step, int64_t step_value, int max_wgs, hipStream_t st);
+// The same gather with each image transformed on its way (augment.hip; the integer spec is in
+// docs/kernels.md and data/augment.py): a random shift of up to `shift` pixels, rotation and
+// zoom, drawn per sample from Philox4x32-10 with counter (dataset index, epoch, 0, 0) and key
+// `seed`.  cosq / sinq (int32 [1024]) and invz (int32 [64]) are the host's Q14 tables.
+void launch_gather_epoch_augment(const uint8_t* images, const int32_t* labels, const int32_t* idx,
+                                 int n, int nimg, uint8_t* out_images, int32_t* out_labels,
+                                 int64_t* ctr, int nctr, int64_t* step, int64_t step_value,
+                                 int max_wgs, const int32_t* cosq, const int32_t* sinq,
+                                 const int32_t* invz, int shift, uint32_t epoch, uint64_t seed,
+                                 hipStream_t st);
 
 // ---------------------------------------------------------------- optimizer
 constexpr int OPT_ADAM = 0;

@@ -23,6 +23,7 @@ import torch
 from . import parallel
 from .config import parse_args
 from .data import sampler
+from .data.augment import spec_from_args
 from .data.mnist import load_split
 from .engine import Trainer
 from .models.reference import MODULES
@@ -189,8 +190,10 @@ def run(args):
                                    channels=spec.channel_bounds())
     dtype = resolve_dtype(args.dtype, args.arch, device)
     reducer0 = reducer
+    # train-time augmentation (--aug-*): training epochs only; --evaluate ignores the flags
+    augment = None if args.evaluate else spec_from_args(args)
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
-                           args.batch_size, use_graphs=args.graphs)
+                           args.batch_size, use_graphs=args.graphs, augment=augment)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises
@@ -216,7 +219,8 @@ def run(args):
                 def check_sync(what, abortable):
                     if device.type == "cuda":
                         parallel.bounded_sync(device, args.timeout, comm, what, abort=abortable)
-                check_structures(program, cands, idx, rank, world_size, check_sync)
+                check_structures(program, cands, idx, rank, world_size, check_sync,
+                                 epoch=args.start_epoch)
         reducer = program.reducer          # (the start-up check may have switched it)
         if args.evaluate:
             test_loss, test_acc = trainer.evaluate()
@@ -242,7 +246,7 @@ def run(args):
 
                 nxt = prefetch.peek(epoch + 1) if program.gpu is not None and \
                     epoch + 1 < args.epochs else None
-                train_loss, train_acc = trainer.train(prefetch.get(epoch), nxt)
+                train_loss, train_acc = trainer.train(prefetch.get(epoch), nxt, epoch)
                 reducer.check()             # xgmi: raise if a peer never arrived
                 test_loss, test_acc = trainer.evaluate()
 

@@ -9,7 +9,8 @@ Additions are opt-in and default to the reference's behaviour:
 ``--momentum``/``--wd`` as the commented-out reference code would,
 :192-194), ``--dtype {fp32,bf16}``, ``--synthetic``/``--synthetic-size``,
 ``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``,
-``--rank-prefix`` and ``--predict-out`` (with ``--evaluate``).
+``--rank-prefix``, ``--predict-out`` (with ``--evaluate``) and the train-time augmentation
+``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``.
 """
 from __future__ import annotations
 
@@ -21,6 +22,19 @@ class _LocalRankAction(argparse.Action):
     def __call__(self, parser, namespace, values, option_string=None):
         setattr(namespace, self.dest, int(values))
         setattr(namespace, "local_rank_given", True)
+
+
+def _ranged(kind, lo, hi):
+    """argparse type: a `kind` (int or float) in [lo, hi]; anything else is a usage error."""
+    def parse(text):
+        try:
+            v = kind(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"invalid {kind.__name__} value: {text!r}")
+        if not lo <= v <= hi:                        # (also rejects nan)
+            raise argparse.ArgumentTypeError(f"{text} is outside {lo}..{hi}")
+        return v
+    return parse
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -104,6 +118,22 @@ def build_parser() -> argparse.ArgumentParser:
                    help='with --evaluate: after the test line, rank 0 writes PATH, a NumPy .npz '
                         'with per-sample log_probs [N, 10], pred [N], labels [N] and the confusion '
                         'matrix [10, 10] of the test set, and prints one accuracy line per class')
+    # train-time augmentation (data/augment.py; no defaults either, for the same reason)
+    g.add_argument('--aug-shift', metavar='N', type=_ranged(int, 0, 8), default=argparse.SUPPRESS,
+                   help='train-time augmentation: random shift of up to N pixels (0..8) per '
+                        'sample and epoch, applied while the epoch is gathered')
+    g.add_argument('--aug-rotate', metavar='DEG', type=_ranged(float, 0.0, 45.0),
+                   default=argparse.SUPPRESS,
+                   help='train-time augmentation: random rotation of up to DEG degrees (0..45)')
+    g.add_argument('--aug-zoom', metavar='F', type=_ranged(float, 0.0, 0.5),
+                   default=argparse.SUPPRESS,
+                   help='train-time augmentation: random zoom by a factor in 1 -/+ F (0..0.5)')
+    g.add_argument('--aug-seed', metavar='N', type=_ranged(int, 0, 2 ** 64 - 1),
+                   default=argparse.SUPPRESS,
+                   help='seed of the augmentation draws (default: --seed if given, else 0); a '
+                        "sample's transform depends on (seed, epoch, dataset index) only. Like "
+                        '--lr, the --aug-* flags are given again on --resume; --evaluate ignores '
+                        'them')
     parser.set_defaults(local_rank_given=False)
     return parser
 

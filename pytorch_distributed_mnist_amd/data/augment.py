@@ -1,0 +1,172 @@
+"""Train-time augmentation: a small random shift, rotation and zoom per sample and epoch.
+
+The transform is integer-only, so the GPU kernel (``csrc/kernels/augment.hip``), this NumPy
+implementation (the CPU path's, and the kernel's oracle) and the tests agree bit for bit.
+A sample's transform depends only on ``(seed, epoch, dataset index)`` -- not on the rank, the
+world size or the sample's position in the epoch's order -- so world-size invariance holds
+and ``--resume`` reproduces an uninterrupted run.
+
+Random numbers: Philox4x32-10, counter ``(dataset_index, epoch, 0, 0)``, key
+``(seed & 0xffffffff, seed >> 32)``, output words ``r0..r3``.  With S the shift range in
+pixels, R the rotation range in degrees and Z the zoom range (a fraction)::
+
+    k = r0 >> 22 (angle level, 0..1023)      j = r1 >> 26 (zoom level, 0..63)
+    dx = r2 % (2S+1) - S                     dy = r3 % (2S+1) - S
+
+Tables (float64, ``np.rint`` to int32)::
+
+    theta_k = radians(R (2k - 1023) / 1023)  cosq[k] = rint(cos theta_k 2^14), sinq likewise
+    z_j = 1 + Z (2j - 63) / 63               invz[j] = rint(2^14 / z_j)
+
+Inverse map (every ``>>`` is an arithmetic shift, i.e. floor)::
+
+    A = (cosq[k] invz[j] + 8192) >> 14       B = (sinq[k] invz[j] + 8192) >> 14
+    output pixel (x, y) in 0..27:  u = 2x - 27, v = 2y - 27
+    SX = (( A u + B v + 64) >> 7) + 3456 - 256 dx          source x in 1/256 px
+    SY = ((-B u + A v + 64) >> 7) + 3456 - 256 dy
+    x0 = SX >> 8, fx = SX & 255, y0 = SY >> 8, fy = SY & 255
+    out = ((256-fx)(256-fy) p(x0,y0) + fx (256-fy) p(x0+1,y0)
+           + (256-fx) fy p(x0,y0+1) + fx fy p(x0+1,y0+1) + 32768) >> 16
+
+with ``p`` zero outside the 28 x 28 image.  Everything fits int32.  S = R = Z = 0 is exactly
+the identity.  Labels are never changed; evaluation and prediction are never augmented.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+MAX_SHIFT = 8
+MAX_ROTATE = 45.0
+MAX_ZOOM = 0.5
+ANGLE_LEVELS = 1024
+ZOOM_LEVELS = 64
+
+_M0, _M1 = 0xD2511F53, 0xCD9E8D57
+_W0, _W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = 0xFFFFFFFF
+
+
+@dataclass(frozen=True)
+class AugmentSpec:
+    """Ranges of the per-sample transform: ``shift`` pixels (0..8), ``rotate`` degrees
+    (0..45), ``zoom`` fraction (0..0.5), and the 64-bit ``seed`` of the Philox key."""
+    shift: int = 0
+    rotate: float = 0.0
+    zoom: float = 0.0
+    seed: int = 0
+
+    def __post_init__(self):
+        if int(self.shift) != self.shift or not 0 <= self.shift <= MAX_SHIFT:
+            raise ValueError(f"shift must be an integer in 0..{MAX_SHIFT}, got {self.shift!r}")
+        if not 0.0 <= self.rotate <= MAX_ROTATE:
+            raise ValueError(f"rotate must be in 0..{MAX_ROTATE} degrees, got {self.rotate!r}")
+        if not 0.0 <= self.zoom <= MAX_ZOOM:
+            raise ValueError(f"zoom must be in 0..{MAX_ZOOM}, got {self.zoom!r}")
+        object.__setattr__(self, "shift", int(self.shift))
+        object.__setattr__(self, "rotate", float(self.rotate))
+        object.__setattr__(self, "zoom", float(self.zoom))
+        object.__setattr__(self, "seed", int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+
+    @property
+    def enabled(self) -> bool:
+        return self.shift > 0 or self.rotate > 0.0 or self.zoom > 0.0
+
+    @property
+    def key(self):
+        return self.seed & _MASK32, self.seed >> 32
+
+    def tables(self):
+        """(cosq int32 [1024], sinq int32 [1024], invz int32 [64]): the Q14 tables."""
+        k = np.arange(ANGLE_LEVELS, dtype=np.float64)
+        theta = np.radians(self.rotate * (2.0 * k - (ANGLE_LEVELS - 1)) / (ANGLE_LEVELS - 1))
+        j = np.arange(ZOOM_LEVELS, dtype=np.float64)
+        z = 1.0 + self.zoom * (2.0 * j - (ZOOM_LEVELS - 1)) / (ZOOM_LEVELS - 1)
+        q = float(1 << 14)
+        return (np.rint(np.cos(theta) * q).astype(np.int32),
+                np.rint(np.sin(theta) * q).astype(np.int32),
+                np.rint(q / z).astype(np.int32))
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10, vectorised: ``counter`` [..., 4] and ``key`` [..., 2] (broadcast against
+    each other) of 32-bit words -> uint32 [..., 4]."""
+    c = np.asarray(counter, dtype=np.uint64) & _MASK32
+    k = np.asarray(key, dtype=np.uint64) & _MASK32
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    m0, m1 = np.uint64(_M0), np.uint64(_M1)
+    mask, s32 = np.uint64(_MASK32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2                   # 32 x 32 -> 64 bits, exact in uint64
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
+        k0 = (k0 + np.uint64(_W0)) & mask
+        k1 = (k1 + np.uint64(_W1)) & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def draw(dataset_index, epoch: int, spec: AugmentSpec):
+    """The per-sample draws (k, j, dx, dy), int64 [N] each."""
+    idx = np.asarray(dataset_index, dtype=np.int64).reshape(-1)
+    ctr = np.zeros((idx.shape[0], 4), dtype=np.uint64)
+    ctr[:, 0] = idx.astype(np.uint64) & _MASK32
+    ctr[:, 1] = int(epoch) & _MASK32
+    r = philox4x32_10(ctr, np.array(spec.key, dtype=np.uint64)).astype(np.int64)
+    span = 2 * spec.shift + 1
+    return r[:, 0] >> 22, r[:, 1] >> 26, r[:, 2] % span - spec.shift, r[:, 3] % span - spec.shift
+
+
+def _u8_rows(images):
+    a = images.numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != 784:
+        raise ValueError(f"images must be uint8 [N, 784], got {a.dtype} {a.shape}")
+    return a
+
+
+def augment_batch(images_u8, dataset_index, epoch: int, spec: AugmentSpec, tables=None):
+    """The transform of ``images_u8`` (uint8 [N, 784], NumPy or host torch) whose rows are the
+    samples ``dataset_index`` [N] of the data set, in epoch ``epoch``: uint8 [N, 784] of the
+    same kind.  ``tables``: ``spec.tables()`` if the caller keeps them."""
+    src = _u8_rows(images_u8)
+    n = src.shape[0]
+    idx = np.asarray(dataset_index.numpy() if isinstance(dataset_index, torch.Tensor)
+                     else dataset_index, dtype=np.int64).reshape(-1)
+    if idx.shape[0] != n:
+        raise ValueError(f"{idx.shape[0]} dataset indices for {n} images")
+    cosq, sinq, invz = tables if tables is not None else spec.tables()
+    k, j, dx, dy = draw(idx, epoch, spec)
+    iz = invz.astype(np.int64)[j]
+    A = ((cosq.astype(np.int64)[k] * iz + 8192) >> 14)[:, None]
+    B = ((sinq.astype(np.int64)[k] * iz + 8192) >> 14)[:, None]
+    pix = np.arange(784, dtype=np.int64)
+    u = (2 * (pix % 28) - 27)[None, :]
+    v = (2 * (pix // 28) - 27)[None, :]
+    sx = ((A * u + B * v + 64) >> 7) + 3456 - 256 * dx[:, None]
+    sy = ((-B * u + A * v + 64) >> 7) + 3456 - 256 * dy[:, None]
+    x0, fx, y0, fy = sx >> 8, sx & 255, sy >> 8, sy & 255
+    rows = np.arange(n)[:, None]
+
+    def p(xx, yy):
+        ok = (xx >= 0) & (xx < 28) & (yy >= 0) & (yy < 28)
+        return np.where(ok, src[rows, np.where(ok, yy * 28 + xx, 0)], 0).astype(np.int64)
+
+    out = ((256 - fx) * (256 - fy) * p(x0, y0) + fx * (256 - fy) * p(x0 + 1, y0)
+           + (256 - fx) * fy * p(x0, y0 + 1) + fx * fy * p(x0 + 1, y0 + 1) + 32768) >> 16
+    out = out.astype(np.uint8)
+    return torch.from_numpy(out) if isinstance(images_u8, torch.Tensor) else out
+
+
+def spec_from_args(args):
+    """The AugmentSpec of a parsed command line (None when no --aug-* range was given):
+    --aug-seed defaults to --seed when that is given, else 0."""
+    shift = getattr(args, "aug_shift", 0)
+    rotate = getattr(args, "aug_rotate", 0.0)
+    zoom = getattr(args, "aug_zoom", 0.0)
+    seed = getattr(args, "aug_seed", None)
+    if seed is None:
+        seed = args.seed if getattr(args, "seed", None) is not None else 0
+    spec = AugmentSpec(shift, rotate, zoom, seed)
+    return spec if spec.enabled else None

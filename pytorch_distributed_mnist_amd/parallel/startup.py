@@ -66,10 +66,11 @@ class StructureCandidate(Candidate):
 
     def __init__(self, name: str, program, apply: Callable[[], None], snap: Snapshot,
                  indices: torch.Tensor, sync: Callable[[str, bool], None], abortable: bool,
-                 devhang: bool = False):
+                 devhang: bool = False, epoch: Optional[int] = None):
         self.name, self.program, self._apply, self.snap = name, program, apply, snap
         self.indices, self._sync, self.abortable = indices, sync, abortable
         self.devhang = devhang
+        self.epoch = epoch                   # of `indices` (the augmentation's draws)
         self._pos = 0
 
     def setup(self) -> None:
@@ -83,7 +84,7 @@ class StructureCandidate(Candidate):
         # left its counters elsewhere); the setup agreement orders every rank's reset before
         # any rank's first launch
         p.reducer.reset_transport()
-        p.set_train_indices(self.indices)
+        p.set_train_indices(self.indices, epoch=self.epoch)
         self._pos = 0
         if p.gpu is not None:
             p.gpu.begin_epoch()
@@ -98,7 +99,7 @@ class StructureCandidate(Candidate):
         buf = p.metrics.buf[0:3]
         for start, size in p._bounds[self._pos:self._pos + k]:
             idx = p.train_idx_cpu[start:start + size]
-            train_step_cpu(p.model, p.arena, p.train_split.images[idx],
+            train_step_cpu(p.model, p.arena, p.train_images_cpu(idx),
                            p.train_split.labels[idx], p.reducer, p.optimizer, buf)
         self._pos += k
         return k
@@ -125,9 +126,11 @@ class StructureCandidate(Candidate):
 
 def check_structures(program, cands: List[tuple], indices: torch.Tensor, rank: int, ws: int,
                      sync: Callable[[str, bool], None], steps: int = 8,
-                     log: Optional[Callable[[str], None]] = None) -> str:
+                     log: Optional[Callable[[str], None]] = None,
+                     epoch: Optional[int] = None) -> str:
     """Run the candidates [(name, apply, abortable)] in preference order until one passes on
     every rank; leave the program on it, with the pre-check training state restored.
+    `epoch`: the epoch number of `indices` (a program that augments needs it).
     Returns the chosen name (raises if none passes)."""
     log = log or (lambda s: print(s, file=sys.stderr, flush=True))
     snap = Snapshot(program)
@@ -135,7 +138,8 @@ def check_structures(program, cands: List[tuple], indices: torch.Tensor, rank: i
     k = max(1, min(int(steps), full // 2 if full >= 2 else 1))
     faults = (knobs.get("PDM_CALIB_FAULT") or "").split(",")
     objs = [StructureCandidate(n, program, fn, snap, indices, sync, ab,
-                               devhang=f"{rank}:{n}:devhang" in faults) for n, fn, ab in cands]
+                               devhang=f"{rank}:{n}:devhang" in faults, epoch=epoch)
+            for n, fn, ab in cands]
     cal = calibrate(objs, ControlPlane(ws), rank, warm_steps=k, timed_steps=k, rounds=1,
                     budget_s=float("inf"), inject=knobs.get("PDM_CALIB_FAULT"),
                     first_ok=True, log=lambda s: None)

@@ -75,7 +75,14 @@ class GpuStepBase:
         self._n_epoch = 0
         self._ctr_host = 0               # the data-step counter's value once the queue drains
         self._dev_step = None            # the optimizer-step count the device holds (host view)
-        self._pending = None             # [order, half, event | None]: the next epoch's gather
+        # [order, half, event | None, epoch | None]: the next epoch's gather
+        self._pending = None
+        # train-time augmentation (data/augment.py): the epoch gather transforms each image;
+        # its Q14 tables are uploaded once, here, never during a capture
+        self.augment = getattr(prog, "augment", None)
+        self._aug_tables = None
+        if self.augment is not None:
+            self._aug_tables = tuple(torch.from_numpy(t).to(dev) for t in self.augment.tables())
         self._epoch_start = 0
         self._gather_stream = None       # stream of the ahead-of-time gathers
         self._ring = None                # pinned staging buffers of the epoch orders
@@ -116,24 +123,34 @@ class GpuStepBase:
         buf[0].copy_(idx)
         return buf
 
-    def _gather(self, idx: torch.Tensor, half: int, stream) -> torch.cuda.Event:
+    def _gather(self, idx: torch.Tensor, half: int, stream, epoch=None) -> torch.cuda.Event:
         """Queue the gather of an epoch order into half `half` of the epoch buffer on `stream`;
-        returns the event behind it."""
+        returns the event behind it.  With augmentation on, the augmenting gather draws the
+        transforms of epoch `epoch`."""
         n = self._n_epoch
         buf = self._stage(idx)
         with torch.cuda.stream(stream):
-            self.C.gather_epoch(self.train_images, self.train_labels, buf[0],
-                                self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
-                                self.ep_labels[half * n:(half + 1) * n],
-                                # one workgroup per 64 rows (grid-striding ones taking
-                                # fewer CUs beside the steps measured no better)
-                                max_wgs=0)
+            if self.augment is None:
+                self.C.gather_epoch(self.train_images, self.train_labels, buf[0],
+                                    self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
+                                    self.ep_labels[half * n:(half + 1) * n],
+                                    # one workgroup per 64 rows (grid-striding ones taking
+                                    # fewer CUs beside the steps measured no better)
+                                    max_wgs=0)
+            else:
+                cosq, sinq, invz = self._aug_tables
+                self.C.gather_epoch_augment(self.train_images, self.train_labels, buf[0],
+                                            self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
+                                            self.ep_labels[half * n:(half + 1) * n],
+                                            max_wgs=0, cosq=cosq, sinq=sinq, invz=invz,
+                                            shift=self.augment.shift, epoch=int(epoch),
+                                            seed=self.augment.seed)
             ev = torch.cuda.Event()
             ev.record(stream)
         buf[1] = ev
         return ev
 
-    def set_train_indices(self, idx_cpu: torch.Tensor, next_idx=None) -> None:
+    def set_train_indices(self, idx_cpu: torch.Tensor, next_idx=None, epoch=None) -> None:
         """Install this epoch's sample order; optionally start materialising the next one's.
 
         ``gather_epoch`` copies an epoch's samples contiguously into one half of the epoch
@@ -148,7 +165,17 @@ class GpuStepBase:
         steps.  At the next boundary that gather has long completed (the host checks its
         event) and the compute stream does not even wait for it: in steady state an epoch
         boundary enqueues nothing.  The host never waits for queued steps.
+
+        ``epoch`` is the epoch number of ``idx_cpu`` (``next_idx`` is epoch + 1's order): with
+        augmentation on, the gathers transform each image by its (seed, epoch, sample) draw,
+        so the number is required; without, it is not used.
         """
+        if self.augment is None:
+            epoch = None
+        elif epoch is None:
+            raise ValueError("augmentation is on: set_train_indices needs the epoch number")
+        else:
+            epoch = int(epoch)
         n = idx_cpu.numel()
         cur = torch.cuda.current_stream(self.device)
         if self._n_epoch != n:
@@ -171,13 +198,14 @@ class GpuStepBase:
             self._ctr_host = start
         half = (start // self.spe) & 1
         p, self._pending = self._pending, None
-        if p is not None and p[0] is idx_cpu and p[1] == half and p[2] is not None:
+        if p is not None and p[0] is idx_cpu and p[1] == half and p[2] is not None and \
+                p[3] == epoch:
             if not p[2].query():         # gathered ahead on the side stream: still running
                 cur.wait_event(p[2])
         else:
             if p is not None and p[2] is not None:
                 cur.wait_event(p[2])     # an unused ahead gather still writes a half
-            self._gather(idx_cpu, half, cur)
+            self._gather(idx_cpu, half, cur, epoch)
         self._epoch_start = start
         if next_idx is not None and next_idx.numel() == n:
             if self._gather_stream is None:
@@ -186,7 +214,7 @@ class GpuStepBase:
                 self._gather_stream = torch.cuda.Stream(self.device)
                 with torch.cuda.stream(self._gather_stream):
                     torch.zeros(1, device=self.device)
-            self._pending = [next_idx, 1 - half, None]
+            self._pending = [next_idx, 1 - half, None, None if epoch is None else epoch + 1]
 
     def _issue_ahead(self) -> None:
         """Queue the next epoch's gather on the side stream once this epoch is half-way
@@ -201,7 +229,7 @@ class GpuStepBase:
         free = torch.cuda.Event()
         free.record(torch.cuda.current_stream(self.device))
         self._gather_stream.wait_event(free)
-        p[2] = self._gather(p[0], p[1], self._gather_stream)
+        p[2] = self._gather(p[0], p[1], self._gather_stream, p[3])
 
     def skip_steps(self, k: int) -> None:
         """Move the data-step counter k steps on within the epoch (bench.py positions its

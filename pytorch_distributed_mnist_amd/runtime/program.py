@@ -21,6 +21,7 @@ from typing import Optional
 
 import torch
 
+from ..data.augment import AugmentSpec, augment_batch
 from ..data.mnist import image_rows, label_vector
 from ..data.sampler import batch_bounds
 from ..utils.metrics import DeviceMetrics
@@ -46,8 +47,15 @@ class Prediction:
 class TrainProgram:
     def __init__(self, model: str, dtype: str, arena, optimizer, reducer, train_split, test_split,
                  batch_size: int, eval_batch: Optional[int] = None, use_graphs: bool = True,
-                 structure: Optional[StepStructure] = None):
+                 structure: Optional[StepStructure] = None,
+                 augment: Optional[AugmentSpec] = None):
         self.model = model
+        # train-time augmentation (data/augment.py): applied to the training batches only --
+        # on the GPU inside the epoch gather, on the CPU per batch.  None or a spec with every
+        # range 0: off, and nothing changes.
+        self.augment = augment if augment is not None and augment.enabled else None
+        self._aug_tables = self.augment.tables() if self.augment is not None else None
+        self._epoch = None
         # how the step is laid out (fusions, band splits, collective placement): read from
         # the PDM_* knobs once, here, unless the caller passes one
         self.structure = structure if structure is not None else StepStructure.from_env()
@@ -80,16 +88,22 @@ class TrainProgram:
             self.gpu = None
 
     # -- epochs ---------------------------------------------------------------
-    def set_train_indices(self, indices: torch.Tensor, next_indices=None) -> None:
+    def set_train_indices(self, indices: torch.Tensor, next_indices=None, epoch=None) -> None:
         """Install this rank's sample order for the coming epoch (and, on the GPU, start
         materialising the next epoch's, ``next_indices``, beside this one's first steps).
 
         GPU: the pinned int32 order the prefetcher hands over is read by the gather kernel in
         place; the batch bounds are arithmetic (full batches, then one ragged tail, as the
-        DataLoader)."""
+        DataLoader).  ``epoch``: the epoch number, which the augmentation's draws depend on
+        (``next_indices`` is epoch + 1's order); required with augmentation on, unused
+        otherwise."""
+        if self.augment is not None and epoch is None:
+            raise ValueError("augmentation is on: set_train_indices needs the epoch number "
+                             "(the transforms are drawn per (seed, epoch, sample))")
         self._n_train = len(indices)
+        self._epoch = None if epoch is None else int(epoch)
         if self.gpu is not None:
-            self.gpu.set_train_indices(indices, next_indices)
+            self.gpu.set_train_indices(indices, next_indices, epoch)
             return
         self.train_idx_cpu = indices.to(torch.int64)
         self._bounds = batch_bounds(len(indices), self.batch_size)
@@ -114,9 +128,17 @@ class TrainProgram:
             buf = self.metrics.buf[0:3]
             for start, size in self._bounds:
                 idx = self.train_idx_cpu[start:start + size]
-                train_step_cpu(self.model, self.arena, self.train_split.images[idx],
+                train_step_cpu(self.model, self.arena, self.train_images_cpu(idx),
                                self.train_split.labels[idx], self.reducer, self.optimizer, buf)
         return self.metrics.read(DeviceMetrics.TRAIN)
+
+    def train_images_cpu(self, idx: torch.Tensor) -> torch.Tensor:
+        """The CPU path's training batch of the samples `idx` (uint8 [len(idx), 784]), augmented
+        for the installed epoch when augmentation is on."""
+        images = self.train_split.images[idx]
+        if self.augment is None:
+            return images
+        return augment_batch(images, idx, self._epoch, self.augment, self._aug_tables)
 
     # -- fc1 optimizer-state sharding (CNN, world size > 1) ------------------------------------
     def shard_supported(self) -> bool:
@@ -240,7 +262,8 @@ class TrainProgram:
 def build_local_program(arch: str, dtype: str, device, batch_size: int, train_split, test_split,
                         optimizer: str = "adam", lr: float = 1e-3, momentum: float = 0.9,
                         weight_decay: float = 1e-4, seed: int = 0, use_graphs: bool = True,
-                        comm=None, force_comm: bool = False, transport: str | None = None):
+                        comm=None, force_comm: bool = False, transport: str | None = None,
+                        augment: Optional[AugmentSpec] = None):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -262,4 +285,4 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                           force=force_comm,
                           transport=transport)
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
-                        use_graphs=use_graphs)
+                        use_graphs=use_graphs, augment=augment)

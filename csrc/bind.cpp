@@ -595,12 +595,18 @@ void fc1_fwd(at::Tensor pool, at::Tensor wf1, at::Tensor part, int64_t B, int64_
                  cur_stream(pool));
 }
 
-void cnn_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
-              at::Tensor bf2, at::Tensor ylab, bool train, c10::optional<at::Tensor> dh,
-              c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
-              at::Tensor metrics, c10::optional<at::Tensor> c0, c10::optional<at::Tensor> c1,
-              c10::optional<at::Tensor> xg, c10::optional<at::Tensor> dh32) {
-  c10::DeviceGuard g(part.device());
+// What cnn_head and cnn_head_dropout check alike: the inputs, and (train) the outputs dh / dht
+// (or dh32) and the per-workgroup slab.
+struct HeadOut {
+  __bf16 *dh = nullptr, *dht = nullptr;
+  float *slab = nullptr, *dh32 = nullptr;
+};
+
+HeadOut check_head(const at::Tensor& part, int64_t splitk, int64_t B, const at::Tensor& bf1,
+                   const at::Tensor& wf2, const at::Tensor& bf2, const at::Tensor& ylab, bool train,
+                   const c10::optional<at::Tensor>& dh, const c10::optional<at::Tensor>& dht,
+                   int64_t ldt, const c10::optional<at::Tensor>& slab, const at::Tensor& metrics,
+                   const c10::optional<at::Tensor>& dh32) {
   TORCH_CHECK(B >= 1, "B must be >= 1");
   need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
   need_min(bf1, at::kFloat, CNN_HID, "bf1");
@@ -611,31 +617,84 @@ void cnn_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Te
   need_numel(ylab, B, "ylab");
   need(metrics, at::kDouble, "metrics");
   need_numel(metrics, 3, "metrics");
-  __bf16 *pdh = nullptr, *pdht = nullptr;
-  float* pslab = nullptr;
-  float* pdh32 = nullptr;
+  HeadOut o;
   if (train) {
     TORCH_CHECK(ldt % 32 == 0 && ldt >= B, "ldt must be a multiple of 32 and >= B");
     TORCH_CHECK(slab, "train mode needs slab");
     if (dh32.has_value() && dh32->defined()) {     // fp32 step: dh in fp32, row-major
       need_min(*dh32, at::kFloat, ldt * CNN_HID, "dh32");
       need_aligned(dh32->data_ptr(), 8, "dh32");
-      pdh32 = dh32->data_ptr<float>();
+      o.dh32 = dh32->data_ptr<float>();
     } else {
       TORCH_CHECK(dh && dht, "train mode needs dh and dht (or dh32)");
       need_min(*dh, at::kBFloat16, ldt * CNN_HID, "dh");
       need_min(*dht, at::kBFloat16, ldt * CNN_HID, "dht");
-      pdh = ptr<__bf16>(*dh);
-      pdht = ptr<__bf16>(*dht);
+      o.dh = ptr<__bf16>(*dh);
+      o.dht = ptr<__bf16>(*dht);
     }
     need_min(*slab, at::kFloat, (int64_t)cnn_head_blocks((int)(ldt / CNN_HEAD_ROWS)) * CNN_HEAD_SLAB,
              "head slab");
-    pslab = slab->data_ptr<float>();
+    o.slab = slab->data_ptr<float>();
   }
+  return o;
+}
+
+void cnn_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
+              at::Tensor bf2, at::Tensor ylab, bool train, c10::optional<at::Tensor> dh,
+              c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
+              at::Tensor metrics, c10::optional<at::Tensor> c0, c10::optional<at::Tensor> c1,
+              c10::optional<at::Tensor> xg, c10::optional<at::Tensor> dh32) {
+  c10::DeviceGuard g(part.device());
+  const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, train, dh, dht, ldt, slab,
+                               metrics, dh32);
   launch_cnn_head(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
-                  wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(), train, pdh,
-                  pdht, (int)ldt, pslab, metrics.data_ptr<double>(), opt_i64(c0), opt_i64(c1),
-                  train ? xg_step(xg) : nullptr, pdh32, cur_stream(part));
+                  wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(), train, o.dh,
+                  o.dht, (int)ldt, o.slab, metrics.data_ptr<double>(), opt_i64(c0), opt_i64(c1),
+                  train ? xg_step(xg) : nullptr, o.dh32, cur_stream(part));
+}
+
+// The dropout mask's arguments (kernels.h launch_cnn_head_dropout): the epoch word (int32 [1]
+// on the device, read as uint32) and the threshold T = round(p * 65536), p in [0, 0.9].
+const uint32_t* check_dropout(const at::Tensor& epoch, int64_t T) {
+  need(epoch, at::kInt, "epoch");
+  need_numel(epoch, 1, "epoch");
+  TORCH_CHECK(T >= 0 && T <= (int64_t)DROPOUT_MAX_T, "T must be in 0..", DROPOUT_MAX_T, ", got ", T);
+  return reinterpret_cast<const uint32_t*>(epoch.data_ptr<int32_t>());
+}
+
+// cnn_head in training mode with dropout on the hidden units (kernels/cnn_head_drop.hip): the
+// same arguments and checks (the train metrics stay untouched, as there), ylab holding label |
+// (dataset index << 4), plus the epoch word, the 64-bit seed, T and the keep scale.
+void cnn_head_dropout(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
+                      at::Tensor bf2, at::Tensor ylab, c10::optional<at::Tensor> dh,
+                      c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
+                      at::Tensor metrics, c10::optional<at::Tensor> c0,
+                      c10::optional<at::Tensor> c1, c10::optional<at::Tensor> xg,
+                      c10::optional<at::Tensor> dh32, at::Tensor epoch, uint64_t seed, int64_t T,
+                      double scale) {
+  c10::DeviceGuard g(part.device());
+  const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, true, dh, dht, ldt, slab,
+                               metrics, dh32);
+  const uint32_t* pe = check_dropout(epoch, T);
+  TORCH_CHECK(scale >= 1.0 && scale <= 65536.0 / (65536.0 - DROPOUT_MAX_T) + 1e-6,
+              "scale must be 65536 / (65536 - T), got ", scale);
+  launch_cnn_head_dropout(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
+                          wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(),
+                          o.dh, o.dht, (int)ldt, o.slab, opt_i64(c0), opt_i64(c1), xg_step(xg),
+                          o.dh32, pe, seed, (uint32_t)T, (float)scale, cur_stream(part));
+}
+
+// The keep mask alone, for the rows of ylab (label | dataset index << 4): uint8 [B, 128].
+at::Tensor dropout_mask_rows(at::Tensor ylab, at::Tensor epoch, uint64_t seed, int64_t T) {
+  c10::DeviceGuard g(ylab.device());
+  need(ylab, at::kInt, "ylab");
+  TORCH_CHECK(ylab.dim() == 1 && ylab.numel() >= 1, "ylab must be [B >= 1]");
+  const uint32_t* pe = check_dropout(epoch, T);
+  const int64_t B = ylab.numel();
+  at::Tensor out = at::empty({B, (int64_t)CNN_HID}, ylab.options().dtype(at::kByte));
+  launch_dropout_mask_rows(ylab.data_ptr<int32_t>(), (int)B, pe, seed, (uint32_t)T,
+                           out.data_ptr<uint8_t>(), cur_stream(ylab));
+  return out;
 }
 
 // ------------------------------------------------------------------ prediction
@@ -1066,6 +1125,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("train"), py::arg("dh"),
         py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
         py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none());
+  m.def("cnn_head_dropout", &cnn_head_dropout, py::arg("part"), py::arg("splitk"), py::arg("B"),
+        py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("dh"),
+        py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
+        py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none(), py::arg("epoch"),
+        py::arg("seed"), py::arg("T"), py::arg("scale"));
+  m.def("dropout_mask_rows", &dropout_mask_rows, py::arg("ylab"), py::arg("epoch"),
+        py::arg("seed"), py::arg("T"));
   m.def("cnn_predict_head", &cnn_predict_head, py::arg("part"), py::arg("splitk"), py::arg("B"),
         py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("logp"),
         py::arg("pred"), py::arg("confusion") = py::none(), py::arg("metrics") = py::none());

@@ -226,6 +226,21 @@ void launch_cnn_head(const float* part, int splitk, int B, const float* bf1, con
                      const float* bf2, const int32_t* ylab, bool train, __bf16* dh, __bf16* dht,
                      int ldt, float* slab, double* metrics, int64_t* c0, int64_t* c1,
                      unsigned* c2, float* dh32, hipStream_t st);
+// cnn_head<train> with dropout on the 128 hidden units (cnn_head_drop.hip; the integer spec is
+// in docs/kernels.md "Dropout head" and data/dropout.py): ylab[row] = label | (dataset index
+// << 4), unit n of sample i in epoch *epoch is kept iff its 16-bit Philox4x32-10 draw (counter
+// (i, *epoch, 1, n >> 3), key `seed`) is >= T, kept units scaled by `scale`.  Same outputs,
+// slab layout and counter bumps as launch_cnn_head(train = true); T = 0, scale = 1 gives its
+// bits.  epoch is a device word, so captured graphs serve every epoch.
+void launch_cnn_head_dropout(const float* part, int splitk, int B, const float* bf1,
+                             const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
+                             __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
+                             unsigned* c2, float* dh32, const uint32_t* epoch, uint64_t seed,
+                             uint32_t T, float scale, hipStream_t st);
+// the keep mask of B rows alone (uint8 [B][128], 1 = kept), from the head's device function
+void launch_dropout_mask_rows(const int32_t* ylab, int B, const uint32_t* epoch, uint64_t seed,
+                              uint32_t T, uint8_t* out, hipStream_t st);
+constexpr uint32_t DROPOUT_MAX_T = 58982;   // round(0.9 * 65536): p is accepted in [0, 0.9]
 void launch_fc1_bwd(const __bf16* dh, const __bf16* dht, int ldt, const __bf16* pool,
                     const __bf16* wf1t, int B, float* gwf1, __bf16* dpool, const float* head_slab,
                     int head_blocks, float* gwf2, float* gbf2, float* gbf1, double* metrics,

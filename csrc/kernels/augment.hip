@@ -19,28 +19,13 @@
 // by the wave's 49 lanes).  The waves never synchronise with each other.
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int AR = 64;                 // rows per workgroup pass (gather_epoch's GR)
 constexpr int AW = AR / 4;             // rows per wave
 constexpr int A_CHUNKS = 784 / 16;     // 49 16-B chunks per image
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
 
 __global__ __launch_bounds__(256) void gather_epoch_augment_kernel(
     const uint8_t* __restrict__ images, const int32_t* __restrict__ labels,

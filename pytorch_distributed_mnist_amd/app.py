@@ -24,6 +24,7 @@ from . import parallel
 from .config import parse_args
 from .data import sampler
 from .data.augment import spec_from_args
+from .data.dropout import spec_from_args as dropout_from_args
 from .data.mnist import load_split
 from .engine import Trainer
 from .models.reference import MODULES
@@ -192,8 +193,11 @@ def run(args):
     reducer0 = reducer
     # train-time augmentation (--aug-*): training epochs only; --evaluate ignores the flags
     augment = None if args.evaluate else spec_from_args(args)
+    # dropout on the CNN's hidden units (--dropout): likewise
+    dropout = None if args.evaluate else dropout_from_args(args)
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
-                           args.batch_size, use_graphs=args.graphs, augment=augment)
+                           args.batch_size, use_graphs=args.graphs, augment=augment,
+                           dropout=dropout)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises

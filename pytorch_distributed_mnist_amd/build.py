@@ -80,6 +80,7 @@ FILE_FLAGS = {
     "kernels/fc1_fwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "kernels/fc1_bwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "kernels/cnn_head.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+    "kernels/cnn_head_drop.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # its twin
 }
 
 

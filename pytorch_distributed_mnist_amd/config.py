@@ -10,7 +10,8 @@ Additions are opt-in and default to the reference's behaviour:
 :192-194), ``--dtype {fp32,bf16}``, ``--synthetic``/``--synthetic-size``,
 ``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``,
 ``--rank-prefix``, ``--predict-out`` (with ``--evaluate``) and the train-time augmentation
-``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``.
+``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``, and dropout on the CNN's
+hidden layer, ``--dropout`` / ``--dropout-seed``.
 """
 from __future__ import annotations
 
@@ -134,6 +135,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "sample's transform depends on (seed, epoch, dataset index) only. Like "
                         '--lr, the --aug-* flags are given again on --resume; --evaluate ignores '
                         'them')
+    # dropout on the CNN's hidden units (data/dropout.py; no defaults, as above: absent = 0 = off)
+    g.add_argument('--dropout', metavar='P', type=_ranged(float, 0.0, 0.9),
+                   default=argparse.SUPPRESS,
+                   help='--arch cnn: drop each of the 128 hidden units in front of fc2 with '
+                        'probability P (0..0.9, default 0 = off) in training steps, kept units '
+                        'scaled by 1 / (1 - P); evaluation never drops')
+    g.add_argument('--dropout-seed', metavar='N', type=_ranged(int, 0, 2 ** 64 - 1),
+                   default=argparse.SUPPRESS,
+                   help='seed of the dropout draws (default: --seed if given, else 0); a unit\'s '
+                        'draw depends on (seed, epoch, dataset index, unit) only. Like --lr, '
+                        '--dropout is given again on --resume; --evaluate ignores it')
     parser.set_defaults(local_rank_given=False)
     return parser
 
@@ -144,4 +156,7 @@ def parse_args(argv=None):
     if hasattr(args, "predict_out") and not args.evaluate:
         parser.error("--predict-out is only valid with --evaluate (it writes the predictions of "
                      "the evaluation pass)")
+    if getattr(args, "dropout", 0.0) > 0.0 and args.arch == "linear":
+        parser.error("argument --dropout: --arch linear has no hidden layer to drop "
+                     "(use --arch cnn)")
     return args

@@ -48,8 +48,13 @@ class CNN(nn.Module):
         return self.fc2(x)
 
 
-def functional_forward(model_name: str, params: dict, x: torch.Tensor) -> torch.Tensor:
-    """Forward of either model from a {torch_name: tensor} dict (torch layouts)."""
+def functional_forward(model_name: str, params: dict, x: torch.Tensor,
+                       hidden_mult: torch.Tensor | None = None) -> torch.Tensor:
+    """Forward of either model from a {torch_name: tensor} dict (torch layouts).  hidden_mult
+    (CNN, training only): a per-row multiplier [N, 128] applied after fc1's ReLU -- the dropout
+    mask times its keep scale (data/dropout.py)."""
+    if hidden_mult is not None and model_name != "cnn":
+        raise ValueError(f"the {model_name} model has no hidden layer to drop")
     if model_name == "linear":
         return F.linear(x.reshape(x.size(0), -1), params["fc.weight"], params["fc.bias"])
     if model_name == "cnn":
@@ -59,6 +64,8 @@ def functional_forward(model_name: str, params: dict, x: torch.Tensor) -> torch.
         h = F.max_pool2d(h, 2)
         h = torch.flatten(h, 1)
         h = F.relu(F.linear(h, params["fc1.weight"], params["fc1.bias"]))
+        if hidden_mult is not None:
+            h = h * hidden_mult
         return F.linear(h, params["fc2.weight"], params["fc2.bias"])
     raise ValueError(f"unknown model {model_name!r}")
 

@@ -156,9 +156,10 @@ class CnnStepF32(GpuStepBase):
                   self.pool, self.pmask, self.a1g, self.xng, self.ylab, spe=self.spe,
                   x3=self.conv_x3, w2x=self.w2x, w2s=self.w2split)
         C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, B, SPLITK_TRAIN, x3=self.conv_x3)
-        C.cnn_head(self.part, SPLITK_TRAIN, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
-                   self.ylab, True, None, None, ldt, self.head_slab, self.metrics.train_view(),
-                   self.ctr[0:1], self.opt._step_dev, None, self.dh32)
+        self.launch_head_train(self.part, SPLITK_TRAIN, B, P["fc1.bias"], P["fc2.weight"],
+                               P["fc2.bias"], self.ylab, None, None, ldt, self.head_slab,
+                               self.metrics.train_view(), self.ctr[0:1], self.opt._step_dev, None,
+                               self.dh32)
         C.f32_fc1_bwd(self.dh32, ldt, self.pool, P["fc1.weight"], B, G["fc1.weight"], self.dpool,
                       self.head_slab, G["fc2.weight"], G["fc2.bias"], G["fc1.bias"],
                       self.metrics.train_view(), x3=self.conv_x3)

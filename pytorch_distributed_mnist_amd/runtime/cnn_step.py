@@ -496,9 +496,9 @@ class CnnStep(GpuStepBase):
             self.reducer.wait_bucket(0)
             self.launch_optimizer(self._bucket_segments()[0])
         C.fc1_fwd(self.pool, self.wf1, self.part, B, S)
-        C.cnn_head(self.part, S, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
-                   True, self.dh, self.dht, ldt, self.head_slab, self.metrics.train_view(),
-                   self.ctr[0:1], self.opt._step_dev, xs)
+        self.launch_head_train(self.part, S, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
+                               self.ylab, self.dh, self.dht, ldt, self.head_slab,
+                               self.metrics.train_view(), self.ctr[0:1], self.opt._step_dev, xs)
         C.fc1_bwd(self.dh, self.dht, ldt, self.pool, self.current_wf1t(), B, G["fc1.weight"], self.dpool,
                   self.head_slab, G["fc2.weight"], G["fc2.bias"], G["fc1.bias"],
                   self.metrics.train_view(),

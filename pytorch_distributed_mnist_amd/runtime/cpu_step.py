@@ -24,11 +24,18 @@ def _leaf_params(arena):
     return leaves, torch_views
 
 
-def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, metrics_buf):
+def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, metrics_buf,
+                   dropout=None, dataset_index=None, epoch=None):
+    """dropout (a data.dropout.DropoutSpec, CNN): the hidden units of the batch's samples
+    `dataset_index` are masked by their (seed, epoch, sample, unit) draws."""
     x = normalize_reference(images_u8)
+    mult = None
+    if dropout is not None:
+        from ..data.dropout import multiplier
+        mult = multiplier(dataset_index, epoch, dropout)
     with torch.enable_grad():
         leaves, views = _leaf_params(arena)
-        logits = functional_forward(model, views, x)
+        logits = functional_forward(model, views, x, mult)
         loss = F.cross_entropy(logits, labels)
         names = [p.name for p in arena.spec.params]
         grads = torch.autograd.grad(loss, [leaves[n] for n in names])

@@ -83,6 +83,18 @@ class GpuStepBase:
         self._aug_tables = None
         if self.augment is not None:
             self._aug_tables = tuple(torch.from_numpy(t).to(dev) for t in self.augment.tables())
+        # dropout on the CNN's hidden units (data/dropout.py): the head draws a row's mask from
+        # its dataset index, which travels in the label word -- the training labels are uploaded
+        # tagged, label | (index << 4), once, here (the gathers and the forward kernels copy
+        # label words verbatim; test labels are never tagged) -- and from the epoch, a device
+        # word that set_train_indices fills in stream order (as the optimizer's lr: the graphs
+        # read the pointer, so one set of graphs serves every epoch)
+        self.dropout = getattr(prog, "dropout", None)
+        self._epoch_dev = None
+        if self.dropout is not None:
+            from ..data.dropout import tag_labels
+            self.train_labels = tag_labels(prog.train_split.labels).to(dev).contiguous()
+            self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._epoch_start = 0
         self._gather_stream = None       # stream of the ahead-of-time gathers
         self._ring = None                # pinned staging buffers of the epoch orders
@@ -168,14 +180,19 @@ class GpuStepBase:
 
         ``epoch`` is the epoch number of ``idx_cpu`` (``next_idx`` is epoch + 1's order): with
         augmentation on, the gathers transform each image by its (seed, epoch, sample) draw,
-        so the number is required; without, it is not used.
+        so the number is required; with dropout on, the head draws its masks from it (the
+        epoch word is filled here, in stream order: behind every step of the previous epoch
+        queued so far, ahead of this epoch's); without either, it is not used.
         """
-        if self.augment is None:
+        if self.augment is None and self.dropout is None:
             epoch = None
         elif epoch is None:
-            raise ValueError("augmentation is on: set_train_indices needs the epoch number")
+            raise ValueError(("augmentation" if self.augment is not None else "dropout") +
+                             " is on: set_train_indices needs the epoch number")
         else:
             epoch = int(epoch)
+            if self.dropout is not None and not 0 <= epoch < 2 ** 31:
+                raise ValueError(f"epoch {epoch} does not fit the device epoch word")
         n = idx_cpu.numel()
         cur = torch.cuda.current_stream(self.device)
         if self._n_epoch != n:
@@ -206,6 +223,8 @@ class GpuStepBase:
             if p is not None and p[2] is not None:
                 cur.wait_event(p[2])     # an unused ahead gather still writes a half
             self._gather(idx_cpu, half, cur, epoch)
+        if self._epoch_dev is not None:
+            self._epoch_dev.fill_(epoch)     # on the compute stream, never inside a capture
         self._epoch_start = start
         if next_idx is not None and next_idx.numel() == n:
             if self._gather_stream is None:
@@ -397,6 +416,20 @@ class GpuStepBase:
 
     def _train_impl(self, B: int) -> None:
         raise NotImplementedError
+
+    def launch_head_train(self, part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab, metrics,
+                          c0, c1, xg=None, dh32=None) -> None:
+        """The CNN programs' training head: cnn_head, or with dropout on its masking twin
+        (cnn_head_drop.hip), which reads the dataset index from the tagged label word and the
+        epoch from the device epoch word."""
+        d = self.dropout
+        if d is None:
+            self.C.cnn_head(part, splitk, B, bf1, wf2, bf2, ylab, True, dh, dht, ldt, slab,
+                            metrics, c0, c1, xg, dh32)
+        else:
+            self.C.cnn_head_dropout(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
+                                    metrics, c0, c1, xg, dh32, self._epoch_dev, d.seed, d.T,
+                                    d.scale)
 
     # -- optimizer ---------------------------------------------------------------
     def optimizer_segments(self):

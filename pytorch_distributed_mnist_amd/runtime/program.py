@@ -22,6 +22,7 @@ from typing import Optional
 import torch
 
 from ..data.augment import AugmentSpec, augment_batch
+from ..data.dropout import DropoutSpec
 from ..data.mnist import image_rows, label_vector
 from ..data.sampler import batch_bounds
 from ..utils.metrics import DeviceMetrics
@@ -48,8 +49,15 @@ class TrainProgram:
     def __init__(self, model: str, dtype: str, arena, optimizer, reducer, train_split, test_split,
                  batch_size: int, eval_batch: Optional[int] = None, use_graphs: bool = True,
                  structure: Optional[StepStructure] = None,
-                 augment: Optional[AugmentSpec] = None):
+                 augment: Optional[AugmentSpec] = None,
+                 dropout: Optional[DropoutSpec] = None):
         self.model = model
+        # dropout on the CNN's hidden units (data/dropout.py): training steps only -- on the GPU
+        # inside the head kernel, on the CPU a multiplier after fc1's ReLU.  None or p = 0: off,
+        # and nothing changes.
+        self.dropout = dropout if dropout is not None and dropout.enabled else None
+        if self.dropout is not None and model != "cnn":
+            raise ValueError(f"dropout needs a hidden layer: the {model} model has none")
         # train-time augmentation (data/augment.py): applied to the training batches only --
         # on the GPU inside the epoch gather, on the CPU per batch.  None or a spec with every
         # range 0: off, and nothing changes.
@@ -94,12 +102,15 @@ class TrainProgram:
 
         GPU: the pinned int32 order the prefetcher hands over is read by the gather kernel in
         place; the batch bounds are arithmetic (full batches, then one ragged tail, as the
-        DataLoader).  ``epoch``: the epoch number, which the augmentation's draws depend on
-        (``next_indices`` is epoch + 1's order); required with augmentation on, unused
-        otherwise."""
+        DataLoader).  ``epoch``: the epoch number, which the augmentation's and the dropout's
+        draws depend on (``next_indices`` is epoch + 1's order); required with either on,
+        unused otherwise."""
         if self.augment is not None and epoch is None:
             raise ValueError("augmentation is on: set_train_indices needs the epoch number "
                              "(the transforms are drawn per (seed, epoch, sample))")
+        if self.dropout is not None and epoch is None:
+            raise ValueError("dropout is on: set_train_indices needs the epoch number "
+                             "(the masks are drawn per (seed, epoch, sample, unit))")
         self._n_train = len(indices)
         self._epoch = None if epoch is None else int(epoch)
         if self.gpu is not None:
@@ -129,7 +140,8 @@ class TrainProgram:
             for start, size in self._bounds:
                 idx = self.train_idx_cpu[start:start + size]
                 train_step_cpu(self.model, self.arena, self.train_images_cpu(idx),
-                               self.train_split.labels[idx], self.reducer, self.optimizer, buf)
+                               self.train_split.labels[idx], self.reducer, self.optimizer, buf,
+                               dropout=self.dropout, dataset_index=idx, epoch=self._epoch)
         return self.metrics.read(DeviceMetrics.TRAIN)
 
     def train_images_cpu(self, idx: torch.Tensor) -> torch.Tensor:
@@ -263,7 +275,8 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                         optimizer: str = "adam", lr: float = 1e-3, momentum: float = 0.9,
                         weight_decay: float = 1e-4, seed: int = 0, use_graphs: bool = True,
                         comm=None, force_comm: bool = False, transport: str | None = None,
-                        augment: Optional[AugmentSpec] = None):
+                        augment: Optional[AugmentSpec] = None,
+                        dropout: Optional[DropoutSpec] = None):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -285,4 +298,4 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                           force=force_comm,
                           transport=transport)
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
-                        use_graphs=use_graphs, augment=augment)
+                        use_graphs=use_graphs, augment=augment, dropout=dropout)

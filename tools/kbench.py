@@ -52,6 +52,7 @@ def main():
       st.train_step(B)
       torch.cuda.synchronize()
       z = torch.zeros(1, dtype=torch.int64, device="cuda")
+      epoch_word = torch.zeros(1, dtype=torch.int32, device="cuda")
       ks = {
           "cnn_fwd": lambda: C.cnn_fwd(st.ep_images.view(-1, 784), st.ep_labels, None, z, B, B,
                                        P["conv1.weight"], P["conv1.bias"], st.w2, P["conv2.bias"],
@@ -60,6 +61,13 @@ def main():
           "cnn_head": lambda: C.cnn_head(st.part, S, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
                                          st.ylab, True, st.dh, st.dht, ldt, st.head_slab,
                                          st.metrics.train_view(), None, None),
+          # the head's masking twin at p = 0.5 (untagged labels: every row draws sample 0's
+          # mask, the same work)
+          "cnn_head_dropout": lambda: C.cnn_head_dropout(st.part, S, B, P["fc1.bias"],
+                                                         P["fc2.weight"], P["fc2.bias"], st.ylab,
+                                                         st.dh, st.dht, ldt, st.head_slab,
+                                                         st.metrics.train_view(), None, None, None,
+                                                         None, epoch_word, 1, 32768, 2.0),
           "fc1_bwd": lambda: C.fc1_bwd(st.dh, st.dht, ldt, st.pool, st.current_wf1t(), B, G["fc1.weight"],
                                        st.dpool, st.head_slab, G["fc2.weight"], G["fc2.bias"],
                                        G["fc1.bias"], st.metrics.train_view(),
@@ -76,7 +84,8 @@ def main():
       line = []
       for name, fn in ks.items():
           us = timeit(fn)
-          tot += us
+          if name != "cnn_head_dropout":   # not a kernel of the default step
+              tot += us
           line.append(f"{name}={us:.1f}")
       st.ctr.zero_()   # each step advances the data counter (rows are clamped past the epoch)
       step = timeit(lambda: st._train_impl(B), 8)

@@ -58,6 +58,29 @@ int64_t* opt_i64(const c10::optional<at::Tensor>& t) {
   return ptr<int64_t>(*t);
 }
 
+// The device-resident learning-rate schedule of the launches that advance the optimizer-step
+// counter (kernels.h LrSched): None, or (table fp64 [n >= 1], cursor int64 [1], lr fp64 [1]).
+LrSched opt_lr_sched(const c10::optional<py::tuple>& t, const int64_t* c1) {
+  LrSched ls;
+  if (!t.has_value()) return ls;
+  TORCH_CHECK(t->size() == 3, "lr_sched: (table, cursor, lr)");
+  TORCH_CHECK(c1 != nullptr, "lr_sched: the learning rate moves on with the optimizer-step "
+                             "counter, which this launch does not advance (c1 is None)");
+  const at::Tensor table = (*t)[0].cast<at::Tensor>();
+  const at::Tensor cursor = (*t)[1].cast<at::Tensor>();
+  const at::Tensor lr = (*t)[2].cast<at::Tensor>();
+  need(table, at::kDouble, "lr_sched table");
+  need(cursor, at::kLong, "lr_sched cursor");
+  need(lr, at::kDouble, "lr_sched lr");
+  TORCH_CHECK(table.numel() >= 1 && table.numel() <= INT32_MAX, "lr_sched table: 1..2^31-1 entries");
+  TORCH_CHECK(cursor.numel() == 1 && lr.numel() == 1, "lr_sched cursor / lr: one element each");
+  ls.table = table.data_ptr<double>();
+  ls.n = (int)table.numel();
+  ls.cursor = cursor.data_ptr<int64_t>();
+  ls.lr = lr.data_ptr<double>();
+  return ls;
+}
+
 // Common checks for the gathered-data inputs of a training step.
 void check_data(const at::Tensor& images, const at::Tensor& labels, const at::Tensor& idx,
                 const at::Tensor& ctr, int64_t bfull, int64_t B) {
@@ -90,7 +113,8 @@ StepRows step_rows(int64_t bfull, int64_t spe, int64_t nrow) {
 // within the buffer); otherwise the sampler gather images[idx[ctr*bfull + i]].
 void lin_train(at::Tensor images, at::Tensor labels, c10::optional<at::Tensor> idx, at::Tensor ctr,
                int64_t bfull, int64_t B, at::Tensor W, at::Tensor b, at::Tensor slab,
-               c10::optional<at::Tensor> metrics, c10::optional<at::Tensor> c1, int64_t spe) {
+               c10::optional<at::Tensor> metrics, c10::optional<at::Tensor> c1, int64_t spe,
+               c10::optional<py::tuple> lr_sched) {
   c10::DeviceGuard g(images.device());
   const bool gather = idx.has_value() && idx->defined();
   TORCH_CHECK(!(gather && spe > 0), "an epoch geometry needs the epoch buffer (idx None)");
@@ -126,7 +150,8 @@ void lin_train(at::Tensor images, at::Tensor labels, c10::optional<at::Tensor> i
   launch_lin_train(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(),
                    gather ? idx->data_ptr<int32_t>() : nullptr, nrow, ctr.data_ptr<int64_t>(),
                    step_rows(bfull, spe, nrow), (int)B, W.data_ptr<float>(), b.data_ptr<float>(),
-                   slab.data_ptr<float>(), mp, opt_i64(c1), cur_stream(images));
+                   slab.data_ptr<float>(), mp, opt_i64(c1), cur_stream(images),
+                   opt_lr_sched(lr_sched, opt_i64(c1)));
 }
 
 void lin_reduce(at::Tensor slab, int64_t B, at::Tensor gW, at::Tensor gb,
@@ -643,14 +668,17 @@ void cnn_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Te
               at::Tensor bf2, at::Tensor ylab, bool train, c10::optional<at::Tensor> dh,
               c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
               at::Tensor metrics, c10::optional<at::Tensor> c0, c10::optional<at::Tensor> c1,
-              c10::optional<at::Tensor> xg, c10::optional<at::Tensor> dh32) {
+              c10::optional<at::Tensor> xg, c10::optional<at::Tensor> dh32,
+              c10::optional<py::tuple> lr_sched) {
   c10::DeviceGuard g(part.device());
+  TORCH_CHECK(train || !lr_sched.has_value(), "lr_sched: only a training head advances it");
   const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, train, dh, dht, ldt, slab,
                                metrics, dh32);
   launch_cnn_head(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
                   wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(), train, o.dh,
                   o.dht, (int)ldt, o.slab, metrics.data_ptr<double>(), opt_i64(c0), opt_i64(c1),
-                  train ? xg_step(xg) : nullptr, o.dh32, cur_stream(part));
+                  train ? xg_step(xg) : nullptr, o.dh32, cur_stream(part),
+                  opt_lr_sched(lr_sched, opt_i64(c1)));
 }
 
 // The dropout mask's arguments (kernels.h launch_cnn_head_dropout): the epoch word (int32 [1]
@@ -671,7 +699,7 @@ void cnn_head_dropout(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1
                       at::Tensor metrics, c10::optional<at::Tensor> c0,
                       c10::optional<at::Tensor> c1, c10::optional<at::Tensor> xg,
                       c10::optional<at::Tensor> dh32, at::Tensor epoch, uint64_t seed, int64_t T,
-                      double scale) {
+                      double scale, c10::optional<py::tuple> lr_sched) {
   c10::DeviceGuard g(part.device());
   const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, true, dh, dht, ldt, slab,
                                metrics, dh32);
@@ -681,7 +709,8 @@ void cnn_head_dropout(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1
   launch_cnn_head_dropout(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
                           wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(),
                           o.dh, o.dht, (int)ldt, o.slab, opt_i64(c0), opt_i64(c1), xg_step(xg),
-                          o.dh32, pe, seed, (uint32_t)T, (float)scale, cur_stream(part));
+                          o.dh32, pe, seed, (uint32_t)T, (float)scale, cur_stream(part),
+                          opt_lr_sched(lr_sched, opt_i64(c1)));
 }
 
 // The keep mask alone, for the rows of ylab (label | dataset index << 4): uint8 [B, 128].
@@ -1086,7 +1115,8 @@ PYBIND11_MODULE(_C, m) {
   m.attr("XG_LOC_DONE") = XG_LOC_DONE;
   m.def("lin_train", &lin_train, py::arg("images"), py::arg("labels"), py::arg("idx"),
         py::arg("ctr"), py::arg("bfull"), py::arg("B"), py::arg("W"), py::arg("b"), py::arg("slab"),
-        py::arg("metrics") = py::none(), py::arg("c1") = py::none(), py::arg("spe") = 0);
+        py::arg("metrics") = py::none(), py::arg("c1") = py::none(), py::arg("spe") = 0,
+        py::arg("lr_sched") = py::none());
   m.def("lin_reduce", &lin_reduce, py::arg("slab"), py::arg("B"), py::arg("gW"), py::arg("gb"),
         py::arg("c0") = py::none(), py::arg("xg") = py::none(), py::arg("metrics") = py::none());
   m.def("lin_eval", &lin_eval);
@@ -1124,12 +1154,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("cnn_head", &cnn_head, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("bf1"),
         py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("train"), py::arg("dh"),
         py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
-        py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none());
+        py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none(),
+        py::arg("lr_sched") = py::none());
   m.def("cnn_head_dropout", &cnn_head_dropout, py::arg("part"), py::arg("splitk"), py::arg("B"),
         py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("dh"),
         py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
         py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none(), py::arg("epoch"),
-        py::arg("seed"), py::arg("T"), py::arg("scale"));
+        py::arg("seed"), py::arg("T"), py::arg("scale"), py::arg("lr_sched") = py::none());
   m.def("dropout_mask_rows", &dropout_mask_rows, py::arg("ylab"), py::arg("epoch"),
         py::arg("seed"), py::arg("T"));
   m.def("cnn_predict_head", &cnn_predict_head, py::arg("part"), py::arg("splitk"), py::arg("B"),

@@ -164,3 +164,17 @@ __device__ __forceinline__ void pdm_bump_counters(int64_t* c0, int64_t* c1,
     if (c2) *c2 += 1;   // xgmi streamed mode: step generation (csrc/xgmi.h)
   }
 }
+
+// The scheduled learning rate (kernels.h LrSched; a template only because this header comes
+// before kernels.h), moved on by the one thread that advances the optimizer-step counter:
+// this step's rate goes into the optimizer's lr word, which nothing reads while this launch
+// runs (its readers are the readers of the step counter).  The clamp is a backstop: the host
+// never queues a step past the table.  Off (table == nullptr): nothing is touched.
+template <class Sched>
+__device__ __forceinline__ void pdm_lr_advance(const Sched& s) {
+  if (s.table != nullptr) {
+    const int64_t i = *s.cursor;
+    *s.lr = s.table[i < 0 ? 0 : (i < s.n ? i : s.n - 1)];
+    *s.cursor = i + 1;
+  }
+}

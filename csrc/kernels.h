@@ -25,6 +25,20 @@ __host__ __device__ __forceinline__ int64_t step_row(const StepRows g, int64_t n
   return (int64_t)(e & 1u) * (nrow >> 1) + s * g.bfull + img;
 }
 
+// Device-resident learning-rate schedule (optim/schedule.py; docs/kernels.md): `table` holds
+// the run's n per-step rates (fp64, computed once on the host), `cursor` the global index of
+// the next optimizer step, `lr` the optimizer's learning-rate word.  The launch that advances
+// the optimizer-step counter also moves lr on (common.h pdm_lr_advance):
+//   i = *cursor;  *lr = table[min(i, n - 1)];  *cursor = i + 1
+// so lr and the step count travel together: whatever is ordered behind that launch for the
+// step counter's sake reads this step's rate.  table == nullptr (the default): off.
+struct LrSched {
+  const double* table = nullptr;
+  int n = 0;
+  int64_t* cursor = nullptr;
+  double* lr = nullptr;
+};
+
 // ---------------------------------------------------------------- linear model
 constexpr int LIN_K = 784;
 constexpr int LIN_N = 10;
@@ -35,10 +49,11 @@ constexpr int LIN_EVAL_ROWS = 16;
 
 // idx == nullptr: rows [ctr*bfull, ctr*bfull + B) of `images` (epoch buffer), else the
 // sampler gather images[idx[ctr*bfull + i]].  metrics (fp64 [3]) and c1 (optimizer-step
-// counter, advanced once) are optional.
+// counter, advanced once, and with it the scheduled learning rate `ls`) are optional.
 void launch_lin_train(const uint8_t* images, const int32_t* labels, const int32_t* idx,
                       int64_t nrow, const int64_t* ctr, StepRows sr, int B, const float* W, const float* b,
-                      float* slab, double* metrics, int64_t* c1, hipStream_t st);
+                      float* slab, double* metrics, int64_t* c1, hipStream_t st,
+                      LrSched ls = LrSched());
 // metrics (optional): one extra workgroup sums the loss / correct slab columns into
 // metrics[0..1] in a fixed order (lin_train only adds the sample count)
 void launch_lin_reduce(const float* slab, int nblk, float* gW, float* gb, int64_t* c0, unsigned* c2,
@@ -225,7 +240,7 @@ void launch_fc1_fwd(const __bf16* pool, const __bf16* wf1, float* part, int B, i
 void launch_cnn_head(const float* part, int splitk, int B, const float* bf1, const float* wf2,
                      const float* bf2, const int32_t* ylab, bool train, __bf16* dh, __bf16* dht,
                      int ldt, float* slab, double* metrics, int64_t* c0, int64_t* c1,
-                     unsigned* c2, float* dh32, hipStream_t st);
+                     unsigned* c2, float* dh32, hipStream_t st, LrSched ls = LrSched());
 // cnn_head<train> with dropout on the 128 hidden units (cnn_head_drop.hip; the integer spec is
 // in docs/kernels.md "Dropout head" and data/dropout.py): ylab[row] = label | (dataset index
 // << 4), unit n of sample i in epoch *epoch is kept iff its 16-bit Philox4x32-10 draw (counter
@@ -236,7 +251,7 @@ void launch_cnn_head_dropout(const float* part, int splitk, int B, const float* 
                              const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
                              __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
                              unsigned* c2, float* dh32, const uint32_t* epoch, uint64_t seed,
-                             uint32_t T, float scale, hipStream_t st);
+                             uint32_t T, float scale, hipStream_t st, LrSched ls = LrSched());
 // the keep mask of B rows alone (uint8 [B][128], 1 = kept), from the head's device function
 void launch_dropout_mask_rows(const int32_t* ylab, int B, const uint32_t* epoch, uint64_t seed,
                               uint32_t T, uint8_t* out, hipStream_t st);

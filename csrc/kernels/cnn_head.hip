@@ -23,7 +23,7 @@ __device__ __forceinline__ void head_body(
     const float* __restrict__ bf1, const float* __restrict__ wf2, const float* __restrict__ bf2,
     const int32_t* __restrict__ ylab, bf16* __restrict__ dh, bf16* __restrict__ dht, int ldt,
     float* __restrict__ slab, double* __restrict__ metrics, int64_t* c0, int64_t* c1, unsigned* c2,
-    float* __restrict__ dh32) {
+    float* __restrict__ dh32, const LrSched ls) {
   static_assert(HEAD_ROWS == 4, "one wave per row, 4 waves");
   __shared__ float hs[HEAD_ROWS][HID];
   __shared__ float dhs[HEAD_ROWS][HID];
@@ -175,6 +175,7 @@ __device__ __forceinline__ void head_body(
     if (c0) *c0 += 1;
     if (c1) *c1 += 1;
     if (c2) *c2 += 1;
+    pdm_lr_advance(ls);                // the step's scheduled learning rate, with its count
   }
   PDM_STAMP(15);
 }
@@ -185,9 +186,10 @@ __global__ __launch_bounds__(256) void cnn_head_kernel(
     const float* __restrict__ part, int S, int B, const float* __restrict__ bf1,
     const float* __restrict__ wf2, const float* __restrict__ bf2, const int32_t* __restrict__ ylab,
     bf16* __restrict__ dh, bf16* __restrict__ dht, int ldt, float* __restrict__ slab,
-    double* __restrict__ metrics, int64_t* c0, int64_t* c1, unsigned* c2, float* __restrict__ dh32) {
+    double* __restrict__ metrics, int64_t* c0, int64_t* c1, unsigned* c2, float* __restrict__ dh32,
+    const LrSched ls) {
   head_body<TRAIN>(blockIdx.x, gridDim.x, part, S, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
-                   metrics, c0, c1, c2, dh32);
+                   metrics, c0, c1, c2, dh32, ls);
 }
 
 }  // namespace
@@ -195,15 +197,16 @@ __global__ __launch_bounds__(256) void cnn_head_kernel(
 void launch_cnn_head(const float* part, int splitk, int B, const float* bf1, const float* wf2,
                      const float* bf2, const int32_t* ylab, bool train, __bf16* dh, __bf16* dht,
                      int ldt, float* slab, double* metrics, int64_t* c0, int64_t* c1,
-                     unsigned* c2, float* dh32, hipStream_t st) {
+                     unsigned* c2, float* dh32, hipStream_t st, LrSched ls) {
   const int groups = (train ? ldt : B + HEAD_ROWS - 1) / HEAD_ROWS;
   const int nblk = cnn_head_blocks(groups);
   if (train)
     cnn_head_kernel<true><<<nblk, 256, 0, st>>>(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt,
-                                                slab, metrics, c0, c1, c2, dh32);
+                                                slab, metrics, c0, c1, c2, dh32, ls);
   else
     cnn_head_kernel<false><<<nblk, 256, 0, st>>>(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht,
-                                                 ldt, slab, metrics, c0, c1, c2, dh32);
+                                                 ldt, slab, metrics, c0, c1, c2, dh32,
+                                                 LrSched());   // evaluation advances nothing
 }
 
 int cnn_head_blocks(int groups) { return groups < CNN_HEAD_MAX_BLOCKS ? groups : CNN_HEAD_MAX_BLOCKS; }

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void cnn_head_dropout_kernel(
     const float* __restrict__ wf2, const float* __restrict__ bf2, const int32_t* __restrict__ ylab,
     bf16* __restrict__ dh, bf16* __restrict__ dht, int ldt, float* __restrict__ slab, int64_t* c0,
     int64_t* c1, unsigned* c2, float* __restrict__ dh32, const uint32_t* __restrict__ epoch_word,
-    uint32_t k0, uint32_t k1, uint32_t T, float scale) {
+    uint32_t k0, uint32_t k1, uint32_t T, float scale, const LrSched ls) {
   static_assert(HEAD_ROWS == 4, "one wave per row, 4 waves");
   __shared__ float hs[HEAD_ROWS][HID];
   __shared__ float dhs[HEAD_ROWS][HID];
@@ -178,6 +178,7 @@ __global__ __launch_bounds__(256) void cnn_head_dropout_kernel(
     if (c0) *c0 += 1;
     if (c1) *c1 += 1;
     if (c2) *c2 += 1;
+    pdm_lr_advance(ls);                // the step's scheduled learning rate, with its count
   }
 }
 
@@ -198,11 +199,11 @@ void launch_cnn_head_dropout(const float* part, int splitk, int B, const float* 
                              const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
                              __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
                              unsigned* c2, float* dh32, const uint32_t* epoch, uint64_t seed,
-                             uint32_t T, float scale, hipStream_t st) {
+                             uint32_t T, float scale, hipStream_t st, LrSched ls) {
   const int nblk = cnn_head_blocks(ldt / HEAD_ROWS);
   cnn_head_dropout_kernel<<<nblk, 256, 0, st>>>(
       part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab, c0, c1, c2, dh32, epoch,
-      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), T, scale);
+      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), T, scale, ls);
 }
 
 void launch_dropout_mask_rows(const int32_t* ylab, int B, const uint32_t* epoch, uint64_t seed,

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(THREADS) void lin_train_kernel(
     const uint8_t* __restrict__ images, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ idx, int64_t nrow, const int64_t* __restrict__ ctr, const StepRows sr,
     int B, const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ slab,
-    double* __restrict__ metrics, int64_t* __restrict__ c1) {
+    double* __restrict__ metrics, int64_t* __restrict__ c1, const LrSched ls) {
   __shared__ __attribute__((aligned(16))) float xs[ROWS][K];
   __shared__ __attribute__((aligned(16))) float dl[ROWS][N];
   __shared__ float lut[256];
@@ -153,8 +153,12 @@ __global__ __launch_bounds__(THREADS) void lin_train_kernel(
     // order; only the sample count is added here (one writer per step)
     if (metrics && blockIdx.x == 0) metrics[2] += (double)B;
   }
-  // nothing in this launch reads the optimizer-step counter
-  if (c1 && blockIdx.x == 0 && tid == 0) *c1 += 1;
+  // nothing in this launch reads the optimizer-step counter, or the learning rate that moves
+  // on with it (kernels.h LrSched)
+  if (blockIdx.x == 0 && tid == 0) {
+    if (c1) *c1 += 1;
+    pdm_lr_advance(ls);
+  }
 }
 
 // world size > 1: fixed-order slab sum into the gradient arena (then the all-reduce)
@@ -239,10 +243,11 @@ __global__ __launch_bounds__(256) void lin_eval_kernel(
 
 void launch_lin_train(const uint8_t* images, const int32_t* labels, const int32_t* idx,
                       int64_t nrow, const int64_t* ctr, StepRows sr, int B, const float* W,
-                      const float* b, float* slab, double* metrics, int64_t* c1, hipStream_t st) {
+                      const float* b, float* slab, double* metrics, int64_t* c1, hipStream_t st,
+                      LrSched ls) {
   const int nblk = (B + ROWS - 1) / ROWS;
   lin_train_kernel<<<nblk, THREADS, 0, st>>>(images, labels, idx, nrow, ctr, sr, B, W, b, slab,
-                                         metrics, c1);
+                                         metrics, c1, ls);
 }
 
 void launch_lin_reduce(const float* slab, int nblk, float* gW, float* gb, int64_t* c0,

@@ -21,7 +21,7 @@ import warnings
 import torch
 
 from . import parallel
-from .config import parse_args
+from .config import parse_args, usage_error
 from .data import sampler
 from .data.augment import spec_from_args
 from .data.dropout import spec_from_args as dropout_from_args
@@ -30,6 +30,7 @@ from .engine import Trainer
 from .models.reference import MODULES
 from .models.specs import get_spec
 from .optim.flat import adjust_learning_rate, build_optimizer
+from .optim.schedule import spec_from_args as schedule_from_args
 from .runtime.arena import FlatArena
 from .runtime.program import TrainProgram
 from .utils import trace
@@ -195,9 +196,18 @@ def run(args):
     augment = None if args.evaluate else spec_from_args(args)
     # dropout on the CNN's hidden units (--dropout): likewise
     dropout = None if args.evaluate else dropout_from_args(args)
+    # per-step learning-rate schedule (--lr-schedule / --lr-warmup / --lr-min): likewise; None
+    # with the defaults, and then the host's per-epoch adjust_learning_rate below is all there is
+    schedule = None
+    if not args.evaluate:
+        spe = -(-sampler.num_samples_per_rank(len(train_split), world_size) // args.batch_size)
+        try:
+            schedule = schedule_from_args(args, spe)
+        except ValueError as e:
+            usage_error(str(e))
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
                            args.batch_size, use_graphs=args.graphs, augment=augment,
-                           dropout=dropout)
+                           dropout=dropout, schedule=schedule)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises
@@ -246,7 +256,8 @@ def run(args):
                                                 int32=program.gpu is not None)
         for epoch in range(args.start_epoch, args.epochs):
             with trace.range("epoch {}".format(epoch)):
-                adjust_learning_rate(optimizer, epoch, args)
+                if schedule is None:    # (else the program sets every step's rate)
+                    adjust_learning_rate(optimizer, epoch, args)
 
                 nxt = prefetch.peek(epoch + 1) if program.gpu is not None and \
                     epoch + 1 < args.epochs else None

@@ -10,8 +10,9 @@ Additions are opt-in and default to the reference's behaviour:
 :192-194), ``--dtype {fp32,bf16}``, ``--synthetic``/``--synthetic-size``,
 ``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``,
 ``--rank-prefix``, ``--predict-out`` (with ``--evaluate``) and the train-time augmentation
-``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``, and dropout on the CNN's
-hidden layer, ``--dropout`` / ``--dropout-seed``.
+``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``, dropout on the CNN's
+hidden layer, ``--dropout`` / ``--dropout-seed``, and the per-step learning-rate schedule
+``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``.
 """
 from __future__ import annotations
 
@@ -146,6 +147,23 @@ def build_parser() -> argparse.ArgumentParser:
                    help='seed of the dropout draws (default: --seed if given, else 0); a unit\'s '
                         'draw depends on (seed, epoch, dataset index, unit) only. Like --lr, '
                         '--dropout is given again on --resume; --evaluate ignores it')
+    # per-step learning-rate schedule (optim/schedule.py; no defaults, as above: absent = the
+    # reference's per-epoch step decay, set by the host)
+    g.add_argument('--lr-schedule', choices=['step', 'constant', 'linear', 'cosine'],
+                   default=argparse.SUPPRESS,
+                   help='learning rate per optimizer step: step (default) = the reference\'s '
+                        'decay by 10 every 10 epochs, constant = --lr, linear / cosine = an '
+                        'anneal from --lr to --lr-min * --lr over the run\'s steps (--epochs x '
+                        'steps per epoch, counted from epoch 0). Like --lr, the --lr-* flags are '
+                        'given again on --resume; --evaluate ignores them')
+    g.add_argument('--lr-warmup', metavar='N', type=_ranged(int, 0, 2 ** 31 - 1),
+                   default=argparse.SUPPRESS,
+                   help='the first N optimizer steps of the run ramp linearly up to the '
+                        'scheduled rate (default 0; fewer than the run\'s steps)')
+    g.add_argument('--lr-min', metavar='F', type=_ranged(float, 0.0, 1.0),
+                   default=argparse.SUPPRESS,
+                   help='--lr-schedule linear / cosine: the final learning rate as a fraction '
+                        'of --lr (0..1, default 0)')
     parser.set_defaults(local_rank_given=False)
     return parser
 
@@ -159,4 +177,14 @@ def parse_args(argv=None):
     if getattr(args, "dropout", 0.0) > 0.0 and args.arch == "linear":
         parser.error("argument --dropout: --arch linear has no hidden layer to drop "
                      "(use --arch cnn)")
+    if hasattr(args, "lr_min") and getattr(args, "lr_schedule", "step") in ("step", "constant"):
+        parser.error("argument --lr-min: --lr-schedule {} has no final rate (use --lr-schedule "
+                     "linear or cosine)".format(getattr(args, "lr_schedule", "step")))
     return args
+
+
+def usage_error(message: str) -> None:
+    """Exit as argparse does for a bad flag (usage, ``error: message``, status 2): for flags
+    that can only be checked once the run's geometry is known (--lr-warmup against the run's
+    steps)."""
+    build_parser().error(message)

@@ -25,9 +25,10 @@ def _leaf_params(arena):
 
 
 def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, metrics_buf,
-                   dropout=None, dataset_index=None, epoch=None):
+                   dropout=None, dataset_index=None, epoch=None, lr=None):
     """dropout (a data.dropout.DropoutSpec, CNN): the hidden units of the batch's samples
-    `dataset_index` are masked by their (seed, epoch, sample, unit) draws."""
+    `dataset_index` are masked by their (seed, epoch, sample, unit) draws.  lr: this step's
+    scheduled learning rate (optim/schedule.py), set on the optimizer before its step."""
     x = normalize_reference(images_u8)
     mult = None
     if dropout is not None:
@@ -47,6 +48,8 @@ def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, met
         for b in range(reducer.num_buckets):
             reducer.bucket_ready(b)
         reducer.finalize()
+        if lr is not None:
+            optimizer.param_groups[0]["lr"] = lr
         sh = getattr(reducer, "shard", None)
         if sh is None:
             optimizer.step_cpu(grad_scale=reducer.grad_scale)

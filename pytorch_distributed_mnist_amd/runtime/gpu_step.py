@@ -10,6 +10,9 @@ kernel reads the data-step counter and only a later kernel advances it; the
 optimizer-step counter is advanced before the optimizer kernel reads it (t >= 1).
 CNN: ``cnn_head`` advances both.  Linear: ``lin_train`` advances the optimizer
 step, ``lin_reduce`` (or, at world size 1, the optimizer launch) the data step.
+With a learning-rate schedule installed (optim/schedule.py), the launch that advances
+the optimizer-step counter also copies the step's rate from the run's table into the
+optimizer's lr word: lr and the step count travel together, to the same readers.
 
 Linear (reference Net, fp32):  lin_train -> [lin_reduce -> all-reduce] -> optim
 CNN (bf16):  cnn_fwd -> fc1_fwd -> cnn_head -> fc1_bwd -> [all-reduce bucket 0]
@@ -95,6 +98,12 @@ class GpuStepBase:
             from ..data.dropout import tag_labels
             self.train_labels = tag_labels(prog.train_split.labels).to(dev).contiguous()
             self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        # per-step learning-rate schedule (optim/schedule.py): the run's table is uploaded once,
+        # here; its pointer, length and the cursor word are baked into the graphs, so one set
+        # of graphs serves every epoch.  The cursor is the global index of the next optimizer
+        # step; begin_epoch puts it at epoch * spe when the device holds something else
+        # (_sched_dev is the host's view of the device word, as _dev_step)
+        self._install_schedule(getattr(prog, "schedule", None))
         self._epoch_start = 0
         self._gather_stream = None       # stream of the ahead-of-time gathers
         self._ring = None                # pinned staging buffers of the epoch orders
@@ -184,6 +193,11 @@ class GpuStepBase:
         epoch word is filled here, in stream order: behind every step of the previous epoch
         queued so far, ahead of this epoch's); without either, it is not used.
         """
+        if self.schedule is not None:
+            if epoch is None:
+                raise ValueError("a learning-rate schedule is on: set_train_indices needs the "
+                                 "epoch number")
+            self._sched_epoch = int(epoch)
         if self.augment is None and self.dropout is None:
             epoch = None
         elif epoch is None:
@@ -207,6 +221,9 @@ class GpuStepBase:
             self.spe = -(-n // self.bfull)
             self.graphs.clear()          # graphs captured the old buffer and geometry
             self._pending = None
+        if self.schedule is not None and self.spe != self.schedule.spe:
+            raise ValueError(f"the learning-rate schedule was built for {self.schedule.spe} "
+                             f"steps per epoch; this epoch has {self.spe}")
         # this epoch starts at the next multiple of spe (a partial epoch before it -- tests,
         # tools -- moves the counter on)
         start = -(-self._ctr_host // self.spe) * self.spe
@@ -255,6 +272,9 @@ class GpuStepBase:
         timed window; every step is the same kernel chain on a different batch)."""
         self.ctr[0:1].add_(k)
         self._ctr_host += k
+        if self.schedule is not None:    # the schedule follows (epoch, step in epoch)
+            self._sched_cursor.add_(k)
+            self._sched_dev += k
         self._issue_ahead()              # as the skipped steps would have
 
     def begin_epoch(self) -> None:
@@ -262,6 +282,44 @@ class GpuStepBase:
         if self._dev_step != self.opt.step_count:
             self.opt.sync_step()
             self._dev_step = self.opt.step_count
+        if self.schedule is not None and self._sched_epoch is not None:
+            # the epoch's first step is global step epoch * spe: written in stream order (never
+            # inside a capture) when the device holds something else -- at the start, on a
+            # resume, after a partial epoch; in steady state the cursor is already there
+            want = self._sched_epoch * self.schedule.spe
+            if self._sched_dev != want:
+                self._sched_cursor.fill_(want)
+                self._sched_dev = want
+
+    def _install_schedule(self, schedule) -> None:
+        self.schedule = schedule
+        self._sched_table = self._sched_cursor = None
+        if schedule is not None:
+            self._sched_table = torch.from_numpy(schedule.table().copy()).to(self.device)
+            self._sched_cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._sched_dev = 0
+        self._sched_epoch = None
+
+    def set_schedule(self, schedule) -> None:
+        """Install (or with None remove) the per-step learning-rate schedule; the graphs bake
+        its table in, so they are re-captured."""
+        if schedule is None and self.schedule is None:
+            return
+        self._install_schedule(schedule)
+        self.invalidate_graphs()
+
+    def lr_sched(self):
+        """The lr_sched argument of the launch that advances the optimizer-step counter (None
+        without a schedule): (table, cursor, the optimizer's lr word)."""
+        if self.schedule is None:
+            return None
+        return (self._sched_table, self._sched_cursor, self.opt._lr_dev)
+
+    def scheduled_lr(self):
+        """The rate of the last step queued (None without a schedule, or before any step)."""
+        if self.schedule is None or self._sched_dev < 1:
+            return None
+        return float(self.schedule.table()[self._sched_dev - 1])
 
     # -- step ------------------------------------------------------------------
     # One hipGraph replay costs ~10-16 us of host time (MI355X_MICROARCH.md price
@@ -355,6 +413,11 @@ class GpuStepBase:
         """Enqueue n consecutive training steps of batch size B."""
         if n <= 0:
             return
+        if self.schedule is not None and self._sched_dev + n > self.schedule.total:
+            # (the kernel's clamp to the last entry is only a backstop)
+            raise RuntimeError(f"{n} steps from global step {self._sched_dev} run past the "
+                               f"learning-rate schedule's {self.schedule.total} steps "
+                               f"({self.schedule.epochs} epochs of {self.schedule.spe})")
         if self.use_graphs:
             plan = self._plan(B, n)
             if self.collective_outside():
@@ -382,6 +445,8 @@ class GpuStepBase:
         self.opt.step_count += n
         if self._dev_step is not None:
             self._dev_step += n
+        if self.schedule is not None:
+            self._sched_dev += n
 
     def train_step(self, B: int) -> None:
         self.train_steps(B, 1)
@@ -425,11 +490,11 @@ class GpuStepBase:
         d = self.dropout
         if d is None:
             self.C.cnn_head(part, splitk, B, bf1, wf2, bf2, ylab, True, dh, dht, ldt, slab,
-                            metrics, c0, c1, xg, dh32)
+                            metrics, c0, c1, xg, dh32, lr_sched=self.lr_sched())
         else:
             self.C.cnn_head_dropout(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
                                     metrics, c0, c1, xg, dh32, self._epoch_dev, d.seed, d.T,
-                                    d.scale)
+                                    d.scale, lr_sched=self.lr_sched())
 
     # -- optimizer ---------------------------------------------------------------
     def optimizer_segments(self):
@@ -553,7 +618,7 @@ class LinearStep(GpuStepBase):
         C = self.C
         C.lin_train(self.ep_images.view(-1, 784), self.ep_labels, None, self.ctr[0:1], self.bfull,
                     B, self.W, self.b, self.slab, self.metrics.train_view(), self.opt._step_dev,
-                    spe=self.spe)
+                    spe=self.spe, lr_sched=self.lr_sched())
         red = self.reducer
         # the step's train loss / correct partials sit in the slabs (columns 7850, 7851): the
         # launch that sums the gradient slabs adds them to the fp64 metrics in a fixed order

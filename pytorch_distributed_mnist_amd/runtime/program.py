@@ -25,6 +25,7 @@ from ..data.augment import AugmentSpec, augment_batch
 from ..data.dropout import DropoutSpec
 from ..data.mnist import image_rows, label_vector
 from ..data.sampler import batch_bounds
+from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
 from .cpu_step import eval_step_cpu, predict_step_cpu, train_step_cpu
 from .structure import StepStructure
@@ -50,8 +51,14 @@ class TrainProgram:
                  batch_size: int, eval_batch: Optional[int] = None, use_graphs: bool = True,
                  structure: Optional[StepStructure] = None,
                  augment: Optional[AugmentSpec] = None,
-                 dropout: Optional[DropoutSpec] = None):
+                 dropout: Optional[DropoutSpec] = None,
+                 schedule: Optional[ScheduleSpec] = None):
         self.model = model
+        # per-step learning-rate schedule (optim/schedule.py): the rate of optimizer step
+        # epoch * spe + i is the run's table entry -- on the GPU copied into the optimizer's lr
+        # word by the launch that advances the step counter, on the CPU set before each step.
+        # None: off, and the optimizer's lr is whatever the host sets (adjust_learning_rate).
+        self.schedule = schedule
         # dropout on the CNN's hidden units (data/dropout.py): training steps only -- on the GPU
         # inside the head kernel, on the CPU a multiplier after fc1's ReLU.  None or p = 0: off,
         # and nothing changes.
@@ -111,6 +118,15 @@ class TrainProgram:
         if self.dropout is not None and epoch is None:
             raise ValueError("dropout is on: set_train_indices needs the epoch number "
                              "(the masks are drawn per (seed, epoch, sample, unit))")
+        if self.schedule is not None:
+            if epoch is None:
+                raise ValueError("a learning-rate schedule is on: set_train_indices needs the "
+                                 "epoch number (the rate follows (epoch, step in epoch))")
+            spe = -(-len(indices) // self.batch_size)
+            if spe != self.schedule.spe or not 0 <= int(epoch) < self.schedule.epochs:
+                raise ValueError(f"the learning-rate schedule covers {self.schedule.epochs} "
+                                 f"epochs of {self.schedule.spe} steps: epoch {epoch} of {spe} "
+                                 "steps is not one of them")
         self._n_train = len(indices)
         self._epoch = None if epoch is None else int(epoch)
         if self.gpu is not None:
@@ -135,14 +151,30 @@ class TrainProgram:
             if self.sync_fn is not None:
                 self.sync_fn("training epoch")
             self.gpu.check_device()
+            lr = self.gpu.scheduled_lr()
+            if lr is not None:
+                # the rate of the last step run, as the reference keeps the last rate it set
+                # (checkpoints); the device word already holds it
+                self.optimizer.param_groups[0]["lr"] = lr
+                self.optimizer._lr_synced = lr
         else:
             buf = self.metrics.buf[0:3]
-            for start, size in self._bounds:
+            table = None if self.schedule is None else self.schedule.table()
+            g0 = 0 if table is None else self._epoch * self.schedule.spe
+            for i, (start, size) in enumerate(self._bounds):
                 idx = self.train_idx_cpu[start:start + size]
                 train_step_cpu(self.model, self.arena, self.train_images_cpu(idx),
                                self.train_split.labels[idx], self.reducer, self.optimizer, buf,
-                               dropout=self.dropout, dataset_index=idx, epoch=self._epoch)
+                               dropout=self.dropout, dataset_index=idx, epoch=self._epoch,
+                               lr=None if table is None else float(table[g0 + i]))
         return self.metrics.read(DeviceMetrics.TRAIN)
+
+    def set_schedule(self, schedule: Optional[ScheduleSpec]) -> None:
+        """Install (or with None remove) the learning-rate schedule; on the GPU the graphs are
+        re-captured on next use."""
+        self.schedule = schedule
+        if self.gpu is not None:
+            self.gpu.set_schedule(schedule)
 
     def train_images_cpu(self, idx: torch.Tensor) -> torch.Tensor:
         """The CPU path's training batch of the samples `idx` (uint8 [len(idx), 784]), augmented
@@ -276,7 +308,8 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                         weight_decay: float = 1e-4, seed: int = 0, use_graphs: bool = True,
                         comm=None, force_comm: bool = False, transport: str | None = None,
                         augment: Optional[AugmentSpec] = None,
-                        dropout: Optional[DropoutSpec] = None):
+                        dropout: Optional[DropoutSpec] = None,
+                        schedule: Optional[ScheduleSpec] = None):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -298,4 +331,5 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                           force=force_comm,
                           transport=transport)
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
-                        use_graphs=use_graphs, augment=augment, dropout=dropout)
+                        use_graphs=use_graphs, augment=augment, dropout=dropout,
+                        schedule=schedule)

@@ -53,6 +53,15 @@ def main():
       torch.cuda.synchronize()
       z = torch.zeros(1, dtype=torch.int64, device="cuda")
       epoch_word = torch.zeros(1, dtype=torch.int32, device="cuda")
+      # the head with a learning-rate schedule on (kernels.h LrSched), beside the same head
+      # advancing the step counter alone: scratch words, a table longer than the calls timed
+      c1 = torch.zeros(1, dtype=torch.int64, device="cuda")
+      sched = (torch.full((4096,), 0.01, dtype=torch.float64, device="cuda"),
+               torch.zeros(1, dtype=torch.int64, device="cuda"),
+               torch.zeros(1, dtype=torch.float64, device="cuda"))
+      head = lambda **kw: C.cnn_head(st.part, S, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
+                                     st.ylab, True, st.dh, st.dht, ldt, st.head_slab,
+                                     st.metrics.train_view(), None, c1, **kw)
       ks = {
           "cnn_fwd": lambda: C.cnn_fwd(st.ep_images.view(-1, 784), st.ep_labels, None, z, B, B,
                                        P["conv1.weight"], P["conv1.bias"], st.w2, P["conv2.bias"],
@@ -68,6 +77,8 @@ def main():
                                                          st.dh, st.dht, ldt, st.head_slab,
                                                          st.metrics.train_view(), None, None, None,
                                                          None, epoch_word, 1, 32768, 2.0),
+          "cnn_head_step": lambda: head(),
+          "cnn_head_sched": lambda: head(lr_sched=sched),
           "fc1_bwd": lambda: C.fc1_bwd(st.dh, st.dht, ldt, st.pool, st.current_wf1t(), B, G["fc1.weight"],
                                        st.dpool, st.head_slab, G["fc2.weight"], G["fc2.bias"],
                                        G["fc1.bias"], st.metrics.train_view(),
@@ -84,7 +95,7 @@ def main():
       line = []
       for name, fn in ks.items():
           us = timeit(fn)
-          if name != "cnn_head_dropout":   # not a kernel of the default step
+          if name not in ("cnn_head_dropout", "cnn_head_step", "cnn_head_sched"):   # variants
               tot += us
           line.append(f"{name}={us:.1f}")
       st.ctr.zero_()   # each step advances the data counter (rows are clamped past the epoch)

@@ -81,6 +81,12 @@ LrSched opt_lr_sched(const c10::optional<py::tuple>& t, const int64_t* c1) {
   return ls;
 }
 
+// --label-smoothing E of the training heads (common.h SmoothTarget): a number in [0, 1].
+float check_smoothing(double e) {
+  TORCH_CHECK(e >= 0.0 && e <= 1.0, "label_smoothing must be in 0..1, got ", e);   // (rejects nan)
+  return (float)e;
+}
+
 // Common checks for the gathered-data inputs of a training step.
 void check_data(const at::Tensor& images, const at::Tensor& labels, const at::Tensor& idx,
                 const at::Tensor& ctr, int64_t bfull, int64_t B) {
@@ -114,8 +120,9 @@ StepRows step_rows(int64_t bfull, int64_t spe, int64_t nrow) {
 void lin_train(at::Tensor images, at::Tensor labels, c10::optional<at::Tensor> idx, at::Tensor ctr,
                int64_t bfull, int64_t B, at::Tensor W, at::Tensor b, at::Tensor slab,
                c10::optional<at::Tensor> metrics, c10::optional<at::Tensor> c1, int64_t spe,
-               c10::optional<py::tuple> lr_sched) {
+               c10::optional<py::tuple> lr_sched, double label_smoothing) {
   c10::DeviceGuard g(images.device());
+  const float eps = check_smoothing(label_smoothing);
   const bool gather = idx.has_value() && idx->defined();
   TORCH_CHECK(!(gather && spe > 0), "an epoch geometry needs the epoch buffer (idx None)");
   int64_t nrow;
@@ -151,7 +158,7 @@ void lin_train(at::Tensor images, at::Tensor labels, c10::optional<at::Tensor> i
                    gather ? idx->data_ptr<int32_t>() : nullptr, nrow, ctr.data_ptr<int64_t>(),
                    step_rows(bfull, spe, nrow), (int)B, W.data_ptr<float>(), b.data_ptr<float>(),
                    slab.data_ptr<float>(), mp, opt_i64(c1), cur_stream(images),
-                   opt_lr_sched(lr_sched, opt_i64(c1)));
+                   opt_lr_sched(lr_sched, opt_i64(c1)), eps);
 }
 
 void lin_reduce(at::Tensor slab, int64_t B, at::Tensor gW, at::Tensor gb,
@@ -681,6 +688,24 @@ void cnn_head(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Te
                   opt_lr_sched(lr_sched, opt_i64(c1)));
 }
 
+// cnn_head in training mode with label-smoothed targets (kernels.h launch_cnn_head_smooth):
+// cnn_head's training arguments and checks (the train metrics stay untouched), plus E.
+void cnn_head_smooth(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
+                     at::Tensor bf2, at::Tensor ylab, c10::optional<at::Tensor> dh,
+                     c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
+                     at::Tensor metrics, c10::optional<at::Tensor> c0, c10::optional<at::Tensor> c1,
+                     c10::optional<at::Tensor> xg, c10::optional<at::Tensor> dh32,
+                     double label_smoothing, c10::optional<py::tuple> lr_sched) {
+  c10::DeviceGuard g(part.device());
+  const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, true, dh, dht, ldt, slab,
+                               metrics, dh32);
+  const float eps = check_smoothing(label_smoothing);
+  launch_cnn_head_smooth(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
+                         wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(),
+                         o.dh, o.dht, (int)ldt, o.slab, opt_i64(c0), opt_i64(c1), xg_step(xg),
+                         o.dh32, eps, cur_stream(part), opt_lr_sched(lr_sched, opt_i64(c1)));
+}
+
 // The dropout mask's arguments (kernels.h launch_cnn_head_dropout): the epoch word (int32 [1]
 // on the device, read as uint32) and the threshold T = round(p * 65536), p in [0, 0.9].
 const uint32_t* check_dropout(const at::Tensor& epoch, int64_t T) {
@@ -692,25 +717,27 @@ const uint32_t* check_dropout(const at::Tensor& epoch, int64_t T) {
 
 // cnn_head in training mode with dropout on the hidden units (kernels/cnn_head_drop.hip): the
 // same arguments and checks (the train metrics stay untouched, as there), ylab holding label |
-// (dataset index << 4), plus the epoch word, the 64-bit seed, T and the keep scale.
+// (dataset index << 4), plus the epoch word, the 64-bit seed, T and the keep scale, and
+// optionally the label smoothing E.
 void cnn_head_dropout(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
                       at::Tensor bf2, at::Tensor ylab, c10::optional<at::Tensor> dh,
                       c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
                       at::Tensor metrics, c10::optional<at::Tensor> c0,
                       c10::optional<at::Tensor> c1, c10::optional<at::Tensor> xg,
                       c10::optional<at::Tensor> dh32, at::Tensor epoch, uint64_t seed, int64_t T,
-                      double scale, c10::optional<py::tuple> lr_sched) {
+                      double scale, c10::optional<py::tuple> lr_sched, double label_smoothing) {
   c10::DeviceGuard g(part.device());
   const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, true, dh, dht, ldt, slab,
                                metrics, dh32);
   const uint32_t* pe = check_dropout(epoch, T);
   TORCH_CHECK(scale >= 1.0 && scale <= 65536.0 / (65536.0 - DROPOUT_MAX_T) + 1e-6,
               "scale must be 65536 / (65536 - T), got ", scale);
+  const float eps = check_smoothing(label_smoothing);
   launch_cnn_head_dropout(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
                           wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(),
                           o.dh, o.dht, (int)ldt, o.slab, opt_i64(c0), opt_i64(c1), xg_step(xg),
                           o.dh32, pe, seed, (uint32_t)T, (float)scale, cur_stream(part),
-                          opt_lr_sched(lr_sched, opt_i64(c1)));
+                          opt_lr_sched(lr_sched, opt_i64(c1)), eps);
 }
 
 // The keep mask alone, for the rows of ylab (label | dataset index << 4): uint8 [B, 128].
@@ -1116,7 +1143,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("lin_train", &lin_train, py::arg("images"), py::arg("labels"), py::arg("idx"),
         py::arg("ctr"), py::arg("bfull"), py::arg("B"), py::arg("W"), py::arg("b"), py::arg("slab"),
         py::arg("metrics") = py::none(), py::arg("c1") = py::none(), py::arg("spe") = 0,
-        py::arg("lr_sched") = py::none());
+        py::arg("lr_sched") = py::none(), py::arg("label_smoothing") = 0.0);
   m.def("lin_reduce", &lin_reduce, py::arg("slab"), py::arg("B"), py::arg("gW"), py::arg("gb"),
         py::arg("c0") = py::none(), py::arg("xg") = py::none(), py::arg("metrics") = py::none());
   m.def("lin_eval", &lin_eval);
@@ -1160,7 +1187,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("dh"),
         py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
         py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none(), py::arg("epoch"),
-        py::arg("seed"), py::arg("T"), py::arg("scale"), py::arg("lr_sched") = py::none());
+        py::arg("seed"), py::arg("T"), py::arg("scale"), py::arg("lr_sched") = py::none(),
+        py::arg("label_smoothing") = 0.0);
+  m.def("cnn_head_smooth", &cnn_head_smooth, py::arg("part"), py::arg("splitk"), py::arg("B"),
+        py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("dh"),
+        py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
+        py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none(),
+        py::arg("label_smoothing"), py::arg("lr_sched") = py::none());
   m.def("dropout_mask_rows", &dropout_mask_rows, py::arg("ylab"), py::arg("epoch"),
         py::arg("seed"), py::arg("T"));
   m.def("cnn_predict_head", &cnn_predict_head, py::arg("part"), py::arg("splitk"), py::arg("B"),

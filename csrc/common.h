@@ -165,6 +165,30 @@ __device__ __forceinline__ void pdm_bump_counters(int64_t* c0, int64_t* c1,
   }
 }
 
+// Label smoothing of the training heads (--label-smoothing E, torch's F.cross_entropy(...,
+// label_smoothing = E) over n classes): the target of class c is (1 - E) [c = y] + E / n, so
+//   dlogits_c = (softmax_c - t_c) / B,   row loss = lse - ((1 - E) l_y + E mean_c l_c)
+//                                                 = nll + E (l_y - mean_c l_c),  nll = lse - l_y.
+// At E = 0 both targets (1 and 0) and the loss (nll + 0 * finite) are exact in fp32: a launch
+// that takes E gives the hard-target bits there.
+struct SmoothTarget {
+  float on, off;
+  __device__ __forceinline__ SmoothTarget(float eps, int n) : off(eps / (float)n) { on = (1.f - eps) + off; }
+  __device__ __forceinline__ float operator()(bool hit) const { return hit ? on : off; }
+};
+// the smoothed row loss from the row's logits (every lane's own registers), its class and its
+// nll; l_y - mean as the mean of the ten differences l_y - l_c, each of the differences' size
+template <int N>
+__device__ __forceinline__ float smooth_loss(const float (&lg)[N], int y, float nll, float eps) {
+  float ly = lg[0];
+#pragma unroll
+  for (int n = 1; n < N; ++n) ly = (n == y) ? lg[n] : ly;
+  float d = 0.f;
+#pragma unroll
+  for (int n = 0; n < N; ++n) d += ly - lg[n];
+  return fmaf(eps, d * (1.f / (float)N), nll);
+}
+
 // The scheduled learning rate (kernels.h LrSched; a template only because this header comes
 // before kernels.h), moved on by the one thread that advances the optimizer-step counter:
 // this step's rate goes into the optimizer's lr word, which nothing reads while this launch

@@ -50,10 +50,12 @@ constexpr int LIN_EVAL_ROWS = 16;
 // idx == nullptr: rows [ctr*bfull, ctr*bfull + B) of `images` (epoch buffer), else the
 // sampler gather images[idx[ctr*bfull + i]].  metrics (fp64 [3]) and c1 (optimizer-step
 // counter, advanced once, and with it the scheduled learning rate `ls`) are optional.
+// label_smoothing (E in 0..1, common.h SmoothTarget): the targets of dlogits and of the loss
+// column; 0 = the hard targets, to the bit.
 void launch_lin_train(const uint8_t* images, const int32_t* labels, const int32_t* idx,
                       int64_t nrow, const int64_t* ctr, StepRows sr, int B, const float* W, const float* b,
                       float* slab, double* metrics, int64_t* c1, hipStream_t st,
-                      LrSched ls = LrSched());
+                      LrSched ls = LrSched(), float label_smoothing = 0.f);
 // metrics (optional): one extra workgroup sums the loss / correct slab columns into
 // metrics[0..1] in a fixed order (lin_train only adds the sample count)
 void launch_lin_reduce(const float* slab, int nblk, float* gW, float* gb, int64_t* c0, unsigned* c2,
@@ -241,17 +243,28 @@ void launch_cnn_head(const float* part, int splitk, int B, const float* bf1, con
                      const float* bf2, const int32_t* ylab, bool train, __bf16* dh, __bf16* dht,
                      int ldt, float* slab, double* metrics, int64_t* c0, int64_t* c1,
                      unsigned* c2, float* dh32, hipStream_t st, LrSched ls = LrSched());
+// cnn_head<train> with label-smoothed targets (docs/kernels.md "Label-smoothing head"):
+// t_c = (1 - E) [c = y] + E / 10 in dlogits and in the loss column (E = label_smoothing in
+// 0..1, a per-run constant); correct, the slab layout, the dh / dh^T / dh32 stores and the
+// counter bumps are launch_cnn_head(train = true)'s, and E = 0 gives its bits.
+void launch_cnn_head_smooth(const float* part, int splitk, int B, const float* bf1,
+                            const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
+                            __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
+                            unsigned* c2, float* dh32, float label_smoothing, hipStream_t st,
+                            LrSched ls = LrSched());
 // cnn_head<train> with dropout on the 128 hidden units (cnn_head_drop.hip; the integer spec is
 // in docs/kernels.md "Dropout head" and data/dropout.py): ylab[row] = label | (dataset index
 // << 4), unit n of sample i in epoch *epoch is kept iff its 16-bit Philox4x32-10 draw (counter
 // (i, *epoch, 1, n >> 3), key `seed`) is >= T, kept units scaled by `scale`.  Same outputs,
 // slab layout and counter bumps as launch_cnn_head(train = true); T = 0, scale = 1 gives its
-// bits.  epoch is a device word, so captured graphs serve every epoch.
+// bits.  epoch is a device word, so captured graphs serve every epoch.  label_smoothing: the
+// targets as in launch_cnn_head_smooth (the class is the label word's low 4 bits); 0 = hard.
 void launch_cnn_head_dropout(const float* part, int splitk, int B, const float* bf1,
                              const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
                              __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
                              unsigned* c2, float* dh32, const uint32_t* epoch, uint64_t seed,
-                             uint32_t T, float scale, hipStream_t st, LrSched ls = LrSched());
+                             uint32_t T, float scale, hipStream_t st, LrSched ls = LrSched(),
+                             float label_smoothing = 0.f);
 // the keep mask of B rows alone (uint8 [B][128], 1 = kept), from the head's device function
 void launch_dropout_mask_rows(const int32_t* ylab, int B, const uint32_t* epoch, uint64_t seed,
                               uint32_t T, uint8_t* out, hipStream_t st);

@@ -4,6 +4,9 @@
 //             and (training) the whole head backward: dlogits, fc2 weight/bias
 //             partials, dh = dlogits.W2 * relu'(h) (bf16, + transposed copy for the
 //             fc1 weight-gradient GEMM), fc1 bias partials; advances step counters.
+//   cnn_head_smooth: cnn_head<train> with label-smoothed targets (--label-smoothing E):
+//             t_c = (1 - E) [c = y] + E / 10 in dlogits and the loss, nothing else differs
+//             (docs/kernels.md "Label-smoothing head").
 // Compiled with the iterative-ilp machine scheduler (build.py FILE_FLAGS).
 #include "cnn_common.h"
 
@@ -16,15 +19,18 @@ using namespace cnn;
 // hidden units 2j, 2j+1, so the fc2 logits are plain wave reductions and the split-K
 // partial loads of a row are spread over a whole wave.
 
-// workgroup blk of nblk (the head's grid)
-template <bool TRAIN>
+// workgroup blk of nblk (the head's grid).  SMOOTH (train only): the targets are smoothed by
+// `eps`, a per-run constant; at eps = 0 every output has the plain head's bits (1 - 0 + 0 / 10 =
+// 1, 0 + 0 / 10 = 0 and loss + 0 * x = loss are exact).
+template <bool TRAIN, bool SMOOTH = false>
 __device__ __forceinline__ void head_body(
     const int blk, const int nblk, const float* __restrict__ part, int S, int B,
     const float* __restrict__ bf1, const float* __restrict__ wf2, const float* __restrict__ bf2,
     const int32_t* __restrict__ ylab, bf16* __restrict__ dh, bf16* __restrict__ dht, int ldt,
     float* __restrict__ slab, double* __restrict__ metrics, int64_t* c0, int64_t* c1, unsigned* c2,
-    float* __restrict__ dh32, const LrSched ls) {
+    float* __restrict__ dh32, const LrSched ls, const float eps = 0.f) {
   static_assert(HEAD_ROWS == 4, "one wave per row, 4 waves");
+  static_assert(TRAIN || !SMOOTH, "evaluation always uses the plain NLL");
   __shared__ float hs[HEAD_ROWS][HID];
   __shared__ float dhs[HEAD_ROWS][HID];
   __shared__ float dls[HEAD_ROWS][NCLS];
@@ -89,7 +95,8 @@ __device__ __forceinline__ void head_body(
     for (int c = 0; c < NCLS; ++c) lg[c] = wave_sum_dpp(fmaf(h.y, w2v[c].y, h.x * w2v[c].x)) + bf2[c];
     float prob[NCLS];
     int correct;
-    const float loss = row_xent<NCLS>(lg, y, prob, correct);
+    float loss = row_xent<NCLS>(lg, y, prob, correct);
+    if (SMOOTH) loss = smooth_loss<NCLS>(lg, y, loss, eps);
     PDM_STAMP(12);
     if (j == 0) {
       red[r][0] = valid ? loss : 0.f;
@@ -99,8 +106,14 @@ __device__ __forceinline__ void head_body(
     if (TRAIN) {
       const float invB = 1.f / (float)B;
       float dl[NCLS];
+      if (SMOOTH) {
+        const SmoothTarget t(eps, NCLS);
 #pragma unroll
-      for (int c = 0; c < NCLS; ++c) dl[c] = valid ? (prob[c] - (c == y ? 1.f : 0.f)) * invB : 0.f;
+        for (int c = 0; c < NCLS; ++c) dl[c] = valid ? (prob[c] - t(c == y)) * invB : 0.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) dl[c] = valid ? (prob[c] - (c == y ? 1.f : 0.f)) * invB : 0.f;
+      }
       float2 dhv = make_float2(0.f, 0.f);
 #pragma unroll
       for (int c = 0; c < NCLS; ++c) {
@@ -192,6 +205,17 @@ __global__ __launch_bounds__(256) void cnn_head_kernel(
                    metrics, c0, c1, c2, dh32, ls);
 }
 
+// the training head with smoothed targets: head_body<true>'s geometry, slab layout, stores,
+// counter bumps and schedule advance
+__global__ __launch_bounds__(256) void cnn_head_smooth_kernel(
+    const float* __restrict__ part, int S, int B, const float* __restrict__ bf1,
+    const float* __restrict__ wf2, const float* __restrict__ bf2, const int32_t* __restrict__ ylab,
+    bf16* __restrict__ dh, bf16* __restrict__ dht, int ldt, float* __restrict__ slab, int64_t* c0,
+    int64_t* c1, unsigned* c2, float* __restrict__ dh32, const LrSched ls, const float eps) {
+  head_body<true, true>(blockIdx.x, gridDim.x, part, S, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
+                        nullptr, c0, c1, c2, dh32, ls, eps);
+}
+
 }  // namespace
 
 void launch_cnn_head(const float* part, int splitk, int B, const float* bf1, const float* wf2,
@@ -207,6 +231,15 @@ void launch_cnn_head(const float* part, int splitk, int B, const float* bf1, con
     cnn_head_kernel<false><<<nblk, 256, 0, st>>>(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht,
                                                  ldt, slab, metrics, c0, c1, c2, dh32,
                                                  LrSched());   // evaluation advances nothing
+}
+
+void launch_cnn_head_smooth(const float* part, int splitk, int B, const float* bf1,
+                            const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
+                            __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
+                            unsigned* c2, float* dh32, float eps, hipStream_t st, LrSched ls) {
+  const int nblk = cnn_head_blocks(ldt / HEAD_ROWS);
+  cnn_head_smooth_kernel<<<nblk, 256, 0, st>>>(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt,
+                                               slab, c0, c1, c2, dh32, ls, eps);
 }
 
 int cnn_head_blocks(int groups) { return groups < CNN_HEAD_MAX_BLOCKS ? groups : CNN_HEAD_MAX_BLOCKS; }

@@ -38,13 +38,15 @@ __device__ __forceinline__ bool dropout_keep_even(uint32_t draw, uint32_t T) { r
 __device__ __forceinline__ bool dropout_keep_odd(uint32_t draw, uint32_t T) { return (draw >> 16) >= T; }
 
 // head_body<true> of cnn_head.hip with the mask between the ReLU and fc2; at T = 0 (scale 1)
-// every output is bit-identical to cnn_head's (tests/test_gpu_dropout.py)
+// every output is bit-identical to cnn_head's (tests/test_gpu_dropout.py).  eps: label
+// smoothing of the targets as in cnn_head_smooth; eps = 0 gives the unsmoothed bits
+// (tests/test_gpu_label_smoothing.py).
 __global__ __launch_bounds__(256) void cnn_head_dropout_kernel(
     const float* __restrict__ part, int S, int B, const float* __restrict__ bf1,
     const float* __restrict__ wf2, const float* __restrict__ bf2, const int32_t* __restrict__ ylab,
     bf16* __restrict__ dh, bf16* __restrict__ dht, int ldt, float* __restrict__ slab, int64_t* c0,
     int64_t* c1, unsigned* c2, float* __restrict__ dh32, const uint32_t* __restrict__ epoch_word,
-    uint32_t k0, uint32_t k1, uint32_t T, float scale, const LrSched ls) {
+    uint32_t k0, uint32_t k1, uint32_t T, float scale, const LrSched ls, const float eps) {
   static_assert(HEAD_ROWS == 4, "one wave per row, 4 waves");
   __shared__ float hs[HEAD_ROWS][HID];
   __shared__ float dhs[HEAD_ROWS][HID];
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(256) void cnn_head_dropout_kernel(
     for (int c = 0; c < NCLS; ++c) lg[c] = wave_sum_dpp(fmaf(hd.y, w2v[c].y, hd.x * w2v[c].x)) + bf2[c];
     float prob[NCLS];
     int correct;
-    const float loss = row_xent<NCLS>(lg, y, prob, correct);
+    const float loss = smooth_loss<NCLS>(lg, y, row_xent<NCLS>(lg, y, prob, correct), eps);
     if (j == 0) {
       red[r][0] = valid ? loss : 0.f;
       red[r][1] = valid ? (float)correct : 0.f;
@@ -123,8 +125,9 @@ __global__ __launch_bounds__(256) void cnn_head_dropout_kernel(
 
     const float invB = 1.f / (float)B;
     float dl[NCLS];
+    const SmoothTarget t(eps, NCLS);
 #pragma unroll
-    for (int c = 0; c < NCLS; ++c) dl[c] = valid ? (prob[c] - (c == y ? 1.f : 0.f)) * invB : 0.f;
+    for (int c = 0; c < NCLS; ++c) dl[c] = valid ? (prob[c] - t(c == y)) * invB : 0.f;
     float2 dhv = make_float2(0.f, 0.f);
 #pragma unroll
     for (int c = 0; c < NCLS; ++c) {
@@ -199,11 +202,11 @@ void launch_cnn_head_dropout(const float* part, int splitk, int B, const float* 
                              const float* wf2, const float* bf2, const int32_t* ylab, __bf16* dh,
                              __bf16* dht, int ldt, float* slab, int64_t* c0, int64_t* c1,
                              unsigned* c2, float* dh32, const uint32_t* epoch, uint64_t seed,
-                             uint32_t T, float scale, hipStream_t st, LrSched ls) {
+                             uint32_t T, float scale, hipStream_t st, LrSched ls, float eps) {
   const int nblk = cnn_head_blocks(ldt / HEAD_ROWS);
   cnn_head_dropout_kernel<<<nblk, 256, 0, st>>>(
       part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab, c0, c1, c2, dh32, epoch,
-      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), T, scale, ls);
+      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), T, scale, ls, eps);
 }
 
 void launch_dropout_mask_rows(const int32_t* ylab, int B, const uint32_t* epoch, uint64_t seed,

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(THREADS) void lin_train_kernel(
     const uint8_t* __restrict__ images, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ idx, int64_t nrow, const int64_t* __restrict__ ctr, const StepRows sr,
     int B, const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ slab,
-    double* __restrict__ metrics, int64_t* __restrict__ c1, const LrSched ls) {
+    double* __restrict__ metrics, int64_t* __restrict__ c1, const LrSched ls, const float eps) {
   __shared__ __attribute__((aligned(16))) float xs[ROWS][K];
   __shared__ __attribute__((aligned(16))) float dl[ROWS][N];
   __shared__ float lut[256];
@@ -99,9 +99,11 @@ __global__ __launch_bounds__(THREADS) void lin_train_kernel(
       if (r < nrows) {
         const int y = lab[r];
         int correct;
-        const float loss = row_xent(l, y, p, correct);
+        // label smoothing (common.h SmoothTarget): eps = 0 is the hard target, to the bit
+        const float loss = smooth_loss<N>(l, y, row_xent(l, y, p, correct), eps);
+        const SmoothTarget t(eps, N);
 #pragma unroll
-        for (int n = 0; n < N; ++n) dl[r][n] = (p[n] - (n == y ? 1.f : 0.f)) * invB;
+        for (int n = 0; n < N; ++n) dl[r][n] = (p[n] - t(n == y)) * invB;
         red[r][0] = loss;
         red[r][1] = (float)correct;
       } else {
@@ -244,10 +246,10 @@ __global__ __launch_bounds__(256) void lin_eval_kernel(
 void launch_lin_train(const uint8_t* images, const int32_t* labels, const int32_t* idx,
                       int64_t nrow, const int64_t* ctr, StepRows sr, int B, const float* W,
                       const float* b, float* slab, double* metrics, int64_t* c1, hipStream_t st,
-                      LrSched ls) {
+                      LrSched ls, float eps) {
   const int nblk = (B + ROWS - 1) / ROWS;
   lin_train_kernel<<<nblk, THREADS, 0, st>>>(images, labels, idx, nrow, ctr, sr, B, W, b, slab,
-                                         metrics, c1, ls);
+                                         metrics, c1, ls, eps);
 }
 
 void launch_lin_reduce(const float* slab, int nblk, float* gW, float* gb, int64_t* c0,

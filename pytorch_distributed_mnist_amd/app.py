@@ -205,9 +205,11 @@ def run(args):
             schedule = schedule_from_args(args, spe)
         except ValueError as e:
             usage_error(str(e))
+    # label smoothing of the training loss (--label-smoothing): likewise
+    smoothing = 0.0 if args.evaluate else getattr(args, "label_smoothing", 0.0)
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
                            args.batch_size, use_graphs=args.graphs, augment=augment,
-                           dropout=dropout, schedule=schedule)
+                           dropout=dropout, schedule=schedule, label_smoothing=smoothing)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises

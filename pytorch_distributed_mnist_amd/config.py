@@ -11,8 +11,9 @@ Additions are opt-in and default to the reference's behaviour:
 ``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``,
 ``--rank-prefix``, ``--predict-out`` (with ``--evaluate``) and the train-time augmentation
 ``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``, dropout on the CNN's
-hidden layer, ``--dropout`` / ``--dropout-seed``, and the per-step learning-rate schedule
-``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``.
+hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
+``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, and label smoothing of the training loss,
+``--label-smoothing``.
 """
 from __future__ import annotations
 
@@ -164,6 +165,13 @@ def build_parser() -> argparse.ArgumentParser:
                    default=argparse.SUPPRESS,
                    help='--lr-schedule linear / cosine: the final learning rate as a fraction '
                         'of --lr (0..1, default 0)')
+    # label smoothing of the training heads (no default, as above: absent = 0 = off)
+    g.add_argument('--label-smoothing', metavar='E', type=_ranged(float, 0.0, 1.0),
+                   default=argparse.SUPPRESS,
+                   help='training steps use the targets (1 - E) * onehot + E / 10 (0..1, default '
+                        '0 = off), as torch\'s cross_entropy(label_smoothing=E); the printed train '
+                        'loss is the smoothed loss, the test loss stays the plain NLL. Like --lr, '
+                        'it is given again on --resume; --evaluate ignores it')
     parser.set_defaults(local_rank_given=False)
     return parser
 

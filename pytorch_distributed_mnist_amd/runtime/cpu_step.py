@@ -25,10 +25,12 @@ def _leaf_params(arena):
 
 
 def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, metrics_buf,
-                   dropout=None, dataset_index=None, epoch=None, lr=None):
+                   dropout=None, dataset_index=None, epoch=None, lr=None, label_smoothing=0.0):
     """dropout (a data.dropout.DropoutSpec, CNN): the hidden units of the batch's samples
     `dataset_index` are masked by their (seed, epoch, sample, unit) draws.  lr: this step's
-    scheduled learning rate (optim/schedule.py), set on the optimizer before its step."""
+    scheduled learning rate (optim/schedule.py), set on the optimizer before its step.
+    label_smoothing (E in 0..1): the criterion's targets are (1 - E) onehot + E / 10, and the
+    loss added to the metrics is the smoothed one."""
     x = normalize_reference(images_u8)
     mult = None
     if dropout is not None:
@@ -37,7 +39,10 @@ def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, met
     with torch.enable_grad():
         leaves, views = _leaf_params(arena)
         logits = functional_forward(model, views, x, mult)
-        loss = F.cross_entropy(logits, labels)
+        if label_smoothing > 0.0:
+            loss = F.cross_entropy(logits, labels, label_smoothing=label_smoothing)
+        else:
+            loss = F.cross_entropy(logits, labels)
         names = [p.name for p in arena.spec.params]
         grads = torch.autograd.grad(loss, [leaves[n] for n in names])
     with torch.no_grad():

@@ -98,6 +98,10 @@ class GpuStepBase:
             from ..data.dropout import tag_labels
             self.train_labels = tag_labels(prog.train_split.labels).to(dev).contiguous()
             self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        # label smoothing of the training heads (--label-smoothing E): a per-run constant, passed
+        # to the head launch as a kernel argument and baked into the graphs; 0: off, and the
+        # step launches the plain heads
+        self.label_smoothing = float(getattr(prog, "label_smoothing", 0.0))
         # per-step learning-rate schedule (optim/schedule.py): the run's table is uploaded once,
         # here; its pointer, length and the cursor word are baked into the graphs, so one set
         # of graphs serves every epoch.  The cursor is the global index of the next optimizer
@@ -486,15 +490,20 @@ class GpuStepBase:
                           c0, c1, xg=None, dh32=None) -> None:
         """The CNN programs' training head: cnn_head, or with dropout on its masking twin
         (cnn_head_drop.hip), which reads the dataset index from the tagged label word and the
-        epoch from the device epoch word."""
-        d = self.dropout
-        if d is None:
-            self.C.cnn_head(part, splitk, B, bf1, wf2, bf2, ylab, True, dh, dht, ldt, slab,
-                            metrics, c0, c1, xg, dh32, lr_sched=self.lr_sched())
-        else:
+        epoch from the device epoch word; with label smoothing on, cnn_head_smooth, or the
+        masking twin with the smoothing passed on."""
+        d, e = self.dropout, self.label_smoothing
+        if d is not None:
+            smooth = dict(label_smoothing=e) if e > 0.0 else {}
             self.C.cnn_head_dropout(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
                                     metrics, c0, c1, xg, dh32, self._epoch_dev, d.seed, d.T,
-                                    d.scale, lr_sched=self.lr_sched())
+                                    d.scale, lr_sched=self.lr_sched(), **smooth)
+        elif e > 0.0:
+            self.C.cnn_head_smooth(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
+                                   metrics, c0, c1, xg, dh32, e, lr_sched=self.lr_sched())
+        else:
+            self.C.cnn_head(part, splitk, B, bf1, wf2, bf2, ylab, True, dh, dht, ldt, slab,
+                            metrics, c0, c1, xg, dh32, lr_sched=self.lr_sched())
 
     # -- optimizer ---------------------------------------------------------------
     def optimizer_segments(self):
@@ -618,7 +627,7 @@ class LinearStep(GpuStepBase):
         C = self.C
         C.lin_train(self.ep_images.view(-1, 784), self.ep_labels, None, self.ctr[0:1], self.bfull,
                     B, self.W, self.b, self.slab, self.metrics.train_view(), self.opt._step_dev,
-                    spe=self.spe, lr_sched=self.lr_sched())
+                    spe=self.spe, lr_sched=self.lr_sched(), label_smoothing=self.label_smoothing)
         red = self.reducer
         # the step's train loss / correct partials sit in the slabs (columns 7850, 7851): the
         # launch that sums the gradient slabs adds them to the fp64 metrics in a fixed order

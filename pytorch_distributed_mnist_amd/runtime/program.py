@@ -52,8 +52,15 @@ class TrainProgram:
                  structure: Optional[StepStructure] = None,
                  augment: Optional[AugmentSpec] = None,
                  dropout: Optional[DropoutSpec] = None,
-                 schedule: Optional[ScheduleSpec] = None):
+                 schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0):
         self.model = model
+        # label smoothing (--label-smoothing E in 0..1): the training steps' targets are
+        # (1 - E) onehot + E / 10, as torch's F.cross_entropy(..., label_smoothing=E) -- on the
+        # GPU inside the head kernels, on the CPU in the criterion.  The training loss is the
+        # smoothed one; evaluation and prediction always use the plain NLL.  0: off.
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing <= 1.0:
+            raise ValueError(f"label_smoothing must be in 0..1, got {label_smoothing}")
         # per-step learning-rate schedule (optim/schedule.py): the rate of optimizer step
         # epoch * spe + i is the run's table entry -- on the GPU copied into the optimizer's lr
         # word by the launch that advances the step counter, on the CPU set before each step.
@@ -166,7 +173,8 @@ class TrainProgram:
                 train_step_cpu(self.model, self.arena, self.train_images_cpu(idx),
                                self.train_split.labels[idx], self.reducer, self.optimizer, buf,
                                dropout=self.dropout, dataset_index=idx, epoch=self._epoch,
-                               lr=None if table is None else float(table[g0 + i]))
+                               lr=None if table is None else float(table[g0 + i]),
+                               label_smoothing=self.label_smoothing)
         return self.metrics.read(DeviceMetrics.TRAIN)
 
     def set_schedule(self, schedule: Optional[ScheduleSpec]) -> None:
@@ -309,7 +317,7 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                         comm=None, force_comm: bool = False, transport: str | None = None,
                         augment: Optional[AugmentSpec] = None,
                         dropout: Optional[DropoutSpec] = None,
-                        schedule: Optional[ScheduleSpec] = None):
+                        schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -332,4 +340,4 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                           transport=transport)
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
                         use_graphs=use_graphs, augment=augment, dropout=dropout,
-                        schedule=schedule)
+                        schedule=schedule, label_smoothing=label_smoothing)

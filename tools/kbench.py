@@ -77,6 +77,12 @@ def main():
                                                          st.dh, st.dht, ldt, st.head_slab,
                                                          st.metrics.train_view(), None, None, None,
                                                          None, epoch_word, 1, 32768, 2.0),
+          # the head with smoothed targets (E = 0.1)
+          "cnn_head_smooth": lambda: C.cnn_head_smooth(st.part, S, B, P["fc1.bias"],
+                                                       P["fc2.weight"], P["fc2.bias"], st.ylab,
+                                                       st.dh, st.dht, ldt, st.head_slab,
+                                                       st.metrics.train_view(), None, None, None,
+                                                       None, 0.1),
           "cnn_head_step": lambda: head(),
           "cnn_head_sched": lambda: head(lr_sched=sched),
           "fc1_bwd": lambda: C.fc1_bwd(st.dh, st.dht, ldt, st.pool, st.current_wf1t(), B, G["fc1.weight"],
@@ -95,7 +101,8 @@ def main():
       line = []
       for name, fn in ks.items():
           us = timeit(fn)
-          if name not in ("cnn_head_dropout", "cnn_head_step", "cnn_head_sched"):   # variants
+          if name not in ("cnn_head_dropout", "cnn_head_smooth", "cnn_head_step",
+                          "cnn_head_sched"):                                        # variants
               tot += us
           line.append(f"{name}={us:.1f}")
       st.ctr.zero_()   # each step advances the data counter (rows are clamped past the epoch)

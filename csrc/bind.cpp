@@ -483,6 +483,42 @@ void optim_step(int64_t kind, at::Tensor p, at::Tensor g, at::Tensor m, c10::opt
   launch_optim((int)kind, a, cur_stream(p));
 }
 
+// Exponential moving average of the weights (ema.hip): ema <- ema + w (params - ema) over the
+// first n floats, on the current stream.  warmup: w is computed on the device from decay and
+// the update index *step_word + offset instead (kernels.h EmaArgs).  nt: nontemporal loads /
+// stores of ema (the variant that measured slower; docs/kernels.md "Weight EMA").
+void ema_update(at::Tensor params, at::Tensor ema, int64_t n, double w, bool warmup, double decay,
+                at::Tensor step_word, int64_t offset, bool nt) {
+  need(params, at::kFloat, "params");
+  need(ema, at::kFloat, "ema");
+  need(step_word, at::kLong, "step_word");
+  c10::DeviceGuard g(params.device());
+  TORCH_CHECK(ema.device() == params.device() && step_word.device() == params.device(),
+              "params, ema and step_word must be on one device");
+  TORCH_CHECK(n >= 1 && n <= params.numel() && n <= ema.numel(), "ema_update: n = ", n,
+              " must be in 1..min(params, ema) = ", std::min(params.numel(), ema.numel()));
+  TORCH_CHECK(step_word.numel() == 1, "step_word: one element");
+  need_aligned(params.data_ptr(), 16, "params");
+  need_aligned(ema.data_ptr(), 16, "ema");
+  // [p, p + n) and [e, e + n) must not overlap: the kernel reads p while it writes e
+  const char* pb = static_cast<const char*>(params.data_ptr());
+  const char* eb = static_cast<const char*>(ema.data_ptr());
+  TORCH_CHECK(pb + 4 * n <= eb || eb + 4 * n <= pb, "params and ema overlap");
+  TORCH_CHECK(decay > 0.0 && decay < 1.0, "ema decay must be in (0, 1), got ", decay);  // (nan too)
+  TORCH_CHECK(w >= 0.0 && w <= 1.0 && (double)(float)w == w,
+              "ema weight must be a float32 value in 0..1, got ", w);
+  EmaArgs a;
+  a.p = ptr<const float>(params);
+  a.e = ptr<float>(ema);
+  a.n = n;
+  a.w = (float)w;
+  a.warmup = warmup ? 1 : 0;
+  a.decay = decay;
+  a.step = ptr<const int64_t>(step_word);
+  a.offset = offset;
+  launch_ema_update(a, nt, cur_stream(params));
+}
+
 // xgmi streamed mode: publish bucket `signal_ch` (-1: none) and wait for the buckets in
 // `waits` = flat (channel, multiplier) pairs, on the current stream (one workgroup)
 void xgmi_wait(at::Tensor sync, int64_t signal_ch, std::vector<int64_t> waits, double timeout_s) {
@@ -1154,6 +1190,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("signal_ch") = -1, py::arg("waits") = std::vector<int64_t>{},
         py::arg("timeout_s") = 60.0, py::arg("bump") = py::none(),
         py::arg("metrics") = py::none(), py::arg("xchg") = py::none(), py::arg("xchg_bucket") = 1);
+  m.def("ema_update", &ema_update, py::arg("params"), py::arg("ema"), py::arg("n"), py::arg("w"),
+        py::arg("warmup"), py::arg("decay"), py::arg("step_word"), py::arg("offset"),
+        py::arg("nt") = false);
   m.def("gather_epoch", &gather_epoch, py::arg("images"), py::arg("labels"), py::arg("idx"),
         py::arg("out_images"), py::arg("out_labels"), py::arg("ctr") = py::none(),
         py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0);

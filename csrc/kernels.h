@@ -161,6 +161,25 @@ struct OptArgs {
 };
 
 void launch_optim(int kind, OptArgs& a, hipStream_t st);
+
+// Exponential moving average of the weights (ema.hip; docs/kernels.md "Weight EMA"), the last
+// launch of a step:  e[i] <- e[i] + w (p[i] - e[i])  over the n floats of the parameter arena,
+// three separately rounded fp32 operations.  warmup == 0: w as passed (float(1 - D)).
+// warmup != 0: w = float(1 - min(decay, (1 + k) / (10 + k))) in fp64 with k = *step + offset,
+// the 1-based index of this update (step: the optimizer-step word, already advanced for this
+// step and only read here).  nt: nontemporal loads / stores of e.
+struct EmaArgs {
+  const float* p;
+  float* e;
+  int64_t n;
+  float w;
+  int warmup;
+  double decay;
+  const int64_t* step;
+  int64_t offset;
+};
+void launch_ema_update(const EmaArgs& a, bool nt, hipStream_t st);
+
 // fc1_fwd switches to 128-row blocks from this batch on (runtime.cnn_step.choose_splitk
 // sizes the split-K for the same tiles)
 constexpr int FC1_BIG_B = 2048;

@@ -30,6 +30,7 @@ from .engine import Trainer
 from .models.reference import MODULES
 from .models.specs import get_spec
 from .optim.flat import adjust_learning_rate, build_optimizer
+from .optim.ema import WeightEma, spec_from_args as ema_from_args
 from .optim.schedule import spec_from_args as schedule_from_args
 from .runtime.arena import FlatArena
 from .runtime.program import TrainProgram
@@ -122,6 +123,7 @@ def structure_candidates(args, program, comm, world_size):
             cands.append(("xgmi-noxchg",
                           lambda: program.use_structure(red, xgmi_exchange=False), False))
         if isinstance(comm, parallel.RcclComm):
+            # (with the weight average on, the only RCCL mode offered: CnnStep.rccl_mode_offered)
             cands.append(("rccl-nocarry", rebuilt("rccl", rccl_mode="nocarry"), True))
         elif mode == "on":
             # the one-GPU rehearsal (xgmi over a gloo control plane): the gloo reducer
@@ -171,6 +173,12 @@ def run(args):
 
     optimizer = build_optimizer(args.optimizer, arena, args)
 
+    # exponential moving average of the weights (--ema-decay / --ema-warmup, optim/ema.py):
+    # every rank's own copy, started at the broadcast weights.  With --evaluate the flag only
+    # selects which of the checkpoint's weights are evaluated, and nothing is averaged.
+    ema_spec = ema_from_args(args)
+    ema = None if ema_spec is None or args.evaluate else WeightEma(ema_spec, arena)
+
     if args.resume:
         if os.path.isfile(args.resume):
             out("=> loading checkpoint '{}'".format(args.resume))
@@ -178,8 +186,21 @@ def run(args):
             args.start_epoch = checkpoint['epoch']
             best_acc = checkpoint['best_acc']
             out("best_acc: {}".format(best_acc))
-            arena.load_state_dict(checkpoint['state_dict'])
+            if ema_spec is not None and args.evaluate:
+                if 'ema_state_dict' not in checkpoint:
+                    raise SystemExit("error: --evaluate --ema-decay: checkpoint '{}' holds no "
+                                     "averaged weights (no ema_state_dict); evaluate it without "
+                                     "--ema-decay".format(args.resume))
+                arena.load_state_dict(checkpoint['ema_state_dict'])
+            else:
+                arena.load_state_dict(checkpoint['state_dict'])
             optimizer.load_state_dict(checkpoint['optimizer'])
+            if ema is not None and 'ema_state_dict' in checkpoint:
+                ema.load_state_dict(checkpoint['ema_state_dict'], checkpoint['ema_updates'])
+            elif ema is not None:
+                ema.reset(arena)
+                out("notice: checkpoint '{}' holds no averaged weights: the average starts at "
+                    "its weights".format(args.resume))
             out("=> loaded checkpoint '{}' (epoch {})".format(args.resume, checkpoint['epoch']))
         else:
             out("=> no checkpoint found at '{}'".format(args.resume))
@@ -209,7 +230,8 @@ def run(args):
     smoothing = 0.0 if args.evaluate else getattr(args, "label_smoothing", 0.0)
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
                            args.batch_size, use_graphs=args.graphs, augment=augment,
-                           dropout=dropout, schedule=schedule, label_smoothing=smoothing)
+                           dropout=dropout, schedule=schedule, label_smoothing=smoothing,
+                           ema=ema)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises
@@ -290,8 +312,8 @@ def run(args):
                 program.sync_master()       # sharded state: every rank gathers the full state
                 if rank == 0:
                     with trace.range("checkpoint"):
-                        save_checkpoint(make_state(epoch + 1, arena, best_acc, optimizer), is_best,
-                                        epoch, directory=args.checkpoint_dir)
+                        save_checkpoint(make_state(epoch + 1, arena, best_acc, optimizer, ema),
+                                        is_best, epoch, directory=args.checkpoint_dir)
     finally:
         if 'prefetch' in locals():
             prefetch.close()

@@ -12,8 +12,9 @@ Additions are opt-in and default to the reference's behaviour:
 ``--rank-prefix``, ``--predict-out`` (with ``--evaluate``) and the train-time augmentation
 ``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``, dropout on the CNN's
 hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
-``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, and label smoothing of the training loss,
-``--label-smoothing``.
+``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
+``--label-smoothing``, and the exponential moving average of the weights, ``--ema-decay`` /
+``--ema-warmup``.
 """
 from __future__ import annotations
 
@@ -38,6 +39,17 @@ def _ranged(kind, lo, hi):
             raise argparse.ArgumentTypeError(f"{text} is outside {lo}..{hi}")
         return v
     return parse
+
+
+def _ema_decay(text):
+    """argparse type of --ema-decay: 0 (off) or a float in the open interval (0, 1)."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid float value: {text!r}")
+    if not 0.0 <= v < 1.0:                           # (also rejects nan)
+        raise argparse.ArgumentTypeError(f"{text} is outside 0 < D < 1 (0 = off)")
+    return v
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -172,6 +184,16 @@ def build_parser() -> argparse.ArgumentParser:
                         '0 = off), as torch\'s cross_entropy(label_smoothing=E); the printed train '
                         'loss is the smoothed loss, the test loss stays the plain NLL. Like --lr, '
                         'it is given again on --resume; --evaluate ignores it')
+    # exponential moving average of the weights (optim/ema.py; no defaults, as above: absent = off)
+    g.add_argument('--ema-decay', metavar='D', type=_ema_decay, default=argparse.SUPPRESS,
+                   help='keep an exponential moving average of the weights, e += (1 - D) (p - e) '
+                        'after every optimizer step (0 < D < 1; default 0 = off): each epoch\'s '
+                        'test line, the model_best choice and the checkpoint\'s ema_state_dict '
+                        'come from it, training is unchanged. Like --lr, it is given again on '
+                        '--resume; with --evaluate it selects the checkpoint\'s averaged weights')
+    g.add_argument('--ema-warmup', action='store_true', default=argparse.SUPPRESS,
+                   help='with --ema-decay: the k-th update uses min(D, (1 + k) / (10 + k)), so '
+                        'the early average follows the weights')
     parser.set_defaults(local_rank_given=False)
     return parser
 
@@ -188,6 +210,8 @@ def parse_args(argv=None):
     if hasattr(args, "lr_min") and getattr(args, "lr_schedule", "step") in ("step", "constant"):
         parser.error("argument --lr-min: --lr-schedule {} has no final rate (use --lr-schedule "
                      "linear or cosine)".format(getattr(args, "lr_schedule", "step")))
+    if hasattr(args, "ema_warmup") and not getattr(args, "ema_decay", 0.0):
+        parser.error("argument --ema-warmup: there is no average to warm up (give --ema-decay D)")
     return args
 
 

@@ -45,11 +45,16 @@ class Snapshot:
         self.params = program.arena.params.detach().clone()
         self.state = {k: v.detach().clone() for k, v in opt.state_buffers().items()}
         self.step = opt.step_count
+        ema = getattr(program, "ema", None)      # the averaged weights and their update count
+        self.ema = None if ema is None else (ema.params.detach().clone(), ema.updates)
 
     @torch.no_grad()
     def restore(self) -> None:
         p, opt = self.program, self.program.optimizer
         p.arena.params.copy_(self.params)
+        if self.ema is not None:
+            p.ema.params.copy_(self.ema[0])
+            p.ema.updates = self.ema[1]
         for k, v in opt.state_buffers().items():
             v.copy_(self.state[k])
         opt.step_count = self.step

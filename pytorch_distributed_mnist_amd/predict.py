@@ -6,7 +6,7 @@ with labels, the confusion matrix.
     out = p.predict(images_u8, labels)        # uint8 [N, 28, 28] or [N, 784], torch or NumPy
     out.log_probs, out.pred, out.confusion
 
-Only the checkpoint's ``state_dict`` is read (the reference's ``module.``-prefixed format,
+Only the checkpoint's ``state_dict`` (with ``ema=True``: its ``ema_state_dict``) is read (the reference's ``module.``-prefixed format,
 ``utils/checkpoint.py``): no optimizer state, no process group and no dataset are needed.  On
 the GPU the images go through the evaluation forward and the prediction head kernels
 (``csrc/kernels/predict.hip``), on the CPU through the torch reference forward.
@@ -46,14 +46,19 @@ class Predictor:
 
 
 def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
-                   dtype: str = "auto") -> Predictor:
+                   dtype: str = "auto", ema: bool = False) -> Predictor:
     """Build ``arch`` ("linear" or "cnn") on ``device`` ("auto", "cuda" or "cpu") and load the
-    checkpoint's weights.  A checkpoint of another architecture raises the arena's
-    ``load_state_dict`` error."""
+    checkpoint's weights -- with ``ema=True`` its averaged weights (``ema_state_dict``, written
+    by runs with ``--ema-decay``; a checkpoint without them raises KeyError).  A checkpoint of
+    another architecture raises the arena's ``load_state_dict`` error."""
     dev = pick_device(0, device)
     spec = get_spec(arch)
     arena = FlatArena(spec, dev)
-    arena.load_state_dict(load_checkpoint(checkpoint_path, map_location="cpu")["state_dict"])
+    checkpoint = load_checkpoint(checkpoint_path, map_location="cpu")
+    if ema and "ema_state_dict" not in checkpoint:
+        raise KeyError(f"checkpoint {checkpoint_path!r} holds no averaged weights "
+                       "(no ema_state_dict): it was written without --ema-decay")
+    arena.load_state_dict(checkpoint["ema_state_dict" if ema else "state_dict"])
     # the program wants an optimizer, a reducer and two splits: a stateless SGD, the
     # one-rank reducer and empty splits (nothing here trains or reads a dataset)
     opt = build_optimizer("sgd", arena, SimpleNamespace(lr=0.0, momentum=0.0, weight_decay=0.0))

@@ -19,11 +19,13 @@ from ..models.specs import ModelSpec
 
 
 class FlatArena:
-    def __init__(self, spec: ModelSpec, device: torch.device):
+    def __init__(self, spec: ModelSpec, device: torch.device, grads: bool = True):
+        """grads=False: a weights-only arena (the averaged weights, optim/ema.py)."""
         self.spec = spec
         self.device = torch.device(device)
         self.params = torch.zeros(spec.total, dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros(spec.total, dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros(spec.total, dtype=torch.float32, device=self.device) \
+            if grads else None
 
     # -- views ---------------------------------------------------------------
     def _view(self, buf: torch.Tensor, name: str) -> torch.Tensor:

@@ -109,11 +109,23 @@ class CnnStepF32(GpuStepBase):
         """Re-derive the split-bf16 copy of conv2's weight (hi = bf16(w), lo = bf16(w - hi))
         from the fp32 master: the optimizer keeps it current after every update, this covers
         any other change (construction, a re-broadcast)."""
-        w = self.arena.param("conv2.weight").reshape(-1)
+        self._split_w2(self.arena, self.w2split)
+
+    @staticmethod
+    def _split_w2(arena, out: torch.Tensor) -> torch.Tensor:
+        w = arena.param("conv2.weight").reshape(-1)
         n = w.numel()
         hi = w.to(torch.bfloat16)
-        self.w2split[:n].copy_(hi)
-        self.w2split[n:].copy_((w - hi.float()).to(torch.bfloat16))
+        out[:n].copy_(hi)
+        out[n:].copy_((w - hi.float()).to(torch.bfloat16))
+        return out
+
+    @torch.no_grad()
+    def weight_set(self, arena):
+        """(name views, conv2's weight as hi / lo planes) of `arena`; fresh tensors, the
+        training copy is not touched."""
+        return ({n: arena.param(n) for n in self.P},
+                self._split_w2(arena, torch.empty_like(self.w2split)))
 
     def _seg(self, p, slab=None):
         """Optimizer segment of parameter p; conv2's weight also writes its hi / lo copy."""
@@ -178,8 +190,9 @@ class CnnStepF32(GpuStepBase):
         red.finalize()
         self.launch_optimizer()
 
-    def evaluate(self) -> None:
-        C, P = self.C, self.P
+    def evaluate(self, ws=None) -> None:
+        C = self.C
+        P, w2split = (self.P, self.w2split) if ws is None else ws
         n = self.test_images.shape[0]
         for s in range(0, n, EVAL_CHUNK):
             b = min(EVAL_CHUNK, n - s)
@@ -187,15 +200,16 @@ class CnnStepF32(GpuStepBase):
             C.f32_fwd(self.test_images[s:s + b], self.test_labels[s:s + b], None, b, b,
                       P["conv1.weight"], P["conv1.bias"], P["conv2.weight"], P["conv2.bias"],
                       self.pool, None, None, None, self.ylab, x3=self.conv_x3,
-                      w2s=self.w2split)
+                      w2s=w2split)
             C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
             C.cnn_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
                        False, None, None, 32, None, self.metrics.eval_view(), None, None)
 
-    def predict(self, images_u8, labels=None):
+    def predict(self, images_u8, labels=None, ws=None):
         """evaluate()'s forward chain over any images, ending in the prediction head
         (csrc/kernels/predict.hip) instead of the metric sums."""
-        C, P = self.C, self.P
+        C = self.C
+        P, w2split = (self.P, self.w2split) if ws is None else ws
         images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
         n = images.shape[0]
         # the forward copies its rows' labels to ylab either way: zeros without labels
@@ -206,7 +220,7 @@ class CnnStepF32(GpuStepBase):
             C.f32_fwd(images[s:s + b], flab[s:s + b], None, b, b,
                       P["conv1.weight"], P["conv1.bias"], P["conv2.weight"], P["conv2.bias"],
                       self.pool, None, None, None, self.ylab, x3=self.conv_x3,
-                      w2s=self.w2split)
+                      w2s=w2split)
             C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
             C.cnn_predict_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
                                self.ylab if lab is not None else None, logp[s:s + b],

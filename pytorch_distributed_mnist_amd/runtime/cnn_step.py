@@ -195,6 +195,7 @@ class CnnStep(GpuStepBase):
         self._shard_rows = None
         self._side = None
         self._side_ev = None
+        self._ema_noticed = False
         self.set_rccl_mode(st.rccl_mode, invalidate=False)
         self.refresh_shadows()
         self._poison_unkept_grads()
@@ -209,11 +210,12 @@ class CnnStep(GpuStepBase):
         """Step structure of the fc bucket on the RCCL data plane (see __init__).  'zero' is
         carry with the fc1 update sharded over the ranks (set_shard_fc); with no reduction
         (world size 1) the structure is moot and 'zero' runs the local step."""
+        if mode not in self.RCCL_MODES + ("zero",):
+            raise ValueError(f"RCCL step mode {mode!r}: choose from {self.RCCL_MODES + ('zero',)}")
+        mode = self.rccl_mode_offered(mode)
         shard = mode == "zero"
         if shard:
             mode = "carry"
-        if mode not in self.RCCL_MODES:
-            raise ValueError(f"RCCL step mode {mode!r}: choose from {self.RCCL_MODES + ('zero',)}")
         self.fc_carry = mode in ("carry", "side")
         self.fc_side = mode == "side"
         self.fc_early = mode == "early"
@@ -224,6 +226,19 @@ class CnnStep(GpuStepBase):
             self.set_shard_fc(True)
         if invalidate:
             self.invalidate_graphs()
+
+    def rccl_mode_offered(self, mode: str) -> str:
+        """The RCCL step mode that runs when `mode` is asked for.  With the weight average on
+        (optim/ema.py) every step's whole weights enter the average in the step's last launch,
+        so the modes that leave the fc bucket's update to a later launch -- carry, side and
+        zero -- are not offered: they become nocarry, with one notice line on rank 0."""
+        if self.ema is None or mode not in ("carry", "side", "zero"):
+            return mode
+        if self.reducer.active and self.reducer.comm.rank == 0 and not self._ema_noticed:
+            self._ema_noticed = True
+            print(f"notice: --ema-decay: the RCCL step mode '{mode}' leaves a step's fc1 update "
+                  "to a later launch; running 'nocarry'", flush=True)
+        return "nocarry"
 
     # -- fc1 optimizer-state sharding --------------------------------------------------------
     def shard_supported(self, reducer=None) -> bool:
@@ -241,6 +256,9 @@ class CnnStep(GpuStepBase):
         """None when the fc1 update can be sharded over `reducer`'s ranks, else why not."""
         red = reducer or self.reducer
         ws = self.shard_world_size(red)
+        if self.ema is not None:
+            return ("the weight average (--ema-decay) takes in every step's whole weights on "
+                    "every rank")
         if not red.active:
             return "no gradient reduction at world size 1"
         if not red.can_shard:
@@ -388,16 +406,21 @@ class CnnStep(GpuStepBase):
         is the one-image cnn_fwd (its grid leaves room for the update's workgroups: B = 256
         53.2 vs 53.9 us per step); the band forward of B <= 128 pays more for them than fc1_bwd
         saves (B = 32: 38.6 vs 37.3; profiles/r5/fc1_carry_local/).  The last step of a
-        train_steps call keeps the fused update."""
+        train_steps call keeps the fused update.  Never with the weight average on: its launch
+        ends every step and takes in the step's whole weights, so the fused update runs on
+        every step, as it does at B <= 128."""
         st = self.structure
         return (not self.reducer.active and self.fuse_fc1 and st.fc1_carry_fwd and
-                st.fc1_carry_local and self.bands(B) == 1)
+                st.fc1_carry_local and self.bands(B) == 1 and self.ema is None)
 
     def _fwd_carry_on(self, B: int) -> bool:
         """SGD: step k's fc1 update runs in step k+1's forward launch (kernels/fc_carry.h) --
         at world size > 1 on the xgmi in-launch-exchange step and the RCCL nocarry step; at
-        world size 1 where _local_carry says so."""
+        world size 1 where _local_carry says so.  Never with the weight average on (see
+        _local_carry)."""
         red = self.reducer
+        if self.ema is not None:
+            return False
         if not red.active:
             return self._local_carry(B)
         if not (self.structure.fc1_carry_fwd and self.opt.kind == "sgd") or self.shard_fc:
@@ -462,6 +485,8 @@ class CnnStep(GpuStepBase):
             # (cin / cout); only the call's last step updates in its own optimizer
             self._train_impl(B, carry_in=carry and i > 0, carry_out=carry and i < n - 1,
                              fwd_in=fwd and (i > 0 or cin), fwd_out=fwd and (i < n - 1 or cout))
+            # (with the average on no structure carries: the step's update is complete)
+            self.launch_ema()
             self.phase = (self.phase + 1) % self.phase_period
         if streamed:
             self.reducer.end()
@@ -670,23 +695,35 @@ class CnnStep(GpuStepBase):
         if self.fuse_fc1 and self.fuse_conv_reduce and not self.keep_grads:
             self.G["fc1.weight"].fill_(float("nan"))
 
-    def evaluate(self) -> None:
-        C, P = self.C, self.P
+    @torch.no_grad()
+    def weight_set(self, arena):
+        """(name views, W2 and W1 as fragment-major bf16) of `arena`, as refresh_shadows derives
+        the training copies; fresh tensors, the training copies are not touched."""
+        bf16 = torch.bfloat16
+        w1 = arena.param("fc1.weight").reshape(128, 9216)
+        w2 = arena.param("conv2.weight").reshape(64, 288)
+        return ({n: arena.param(n) for n in self.P}, frag_major(w2.to(bf16)),
+                frag_major(w1.to(bf16)))
+
+    def evaluate(self, ws=None) -> None:
+        C = self.C
+        P, w2, wf1 = (self.P, self.w2, self.wf1) if ws is None else ws
         n = self.test_images.shape[0]
         S = self.splitk_eval
         for s in range(0, n, EVAL_CHUNK):
             b = min(EVAL_CHUNK, n - s)
             C.cnn_fwd(self.test_images[s:s + b], self.test_labels[s:s + b], None, None, b, b,
-                      P["conv1.weight"], P["conv1.bias"], self.w2, P["conv2.bias"], self.pool,
+                      P["conv1.weight"], P["conv1.bias"], w2, P["conv2.bias"], self.pool,
                       self.pmask, None, self.ylab)
-            C.fc1_fwd(self.pool, self.wf1, self.part, b, S)
+            C.fc1_fwd(self.pool, wf1, self.part, b, S)
             C.cnn_head(self.part, S, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
                        False, None, None, 32, None, self.metrics.eval_view(), None, None)
 
-    def predict(self, images_u8, labels=None):
+    def predict(self, images_u8, labels=None, ws=None):
         """evaluate()'s forward chain over any images, ending in the prediction head
         (csrc/kernels/predict.hip) instead of the metric sums."""
-        C, P = self.C, self.P
+        C = self.C
+        P, w2, wf1 = (self.P, self.w2, self.wf1) if ws is None else ws
         images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
         n = images.shape[0]
         # the forward copies its rows' labels to ylab either way: zeros without labels
@@ -695,9 +732,9 @@ class CnnStep(GpuStepBase):
         for s in range(0, n, EVAL_CHUNK):
             b = min(EVAL_CHUNK, n - s)
             C.cnn_fwd(images[s:s + b], flab[s:s + b], None, None, b, b,
-                      P["conv1.weight"], P["conv1.bias"], self.w2, P["conv2.bias"], self.pool,
+                      P["conv1.weight"], P["conv1.bias"], w2, P["conv2.bias"], self.pool,
                       self.pmask, None, self.ylab)
-            C.fc1_fwd(self.pool, self.wf1, self.part, b, S)
+            C.fc1_fwd(self.pool, wf1, self.part, b, S)
             C.cnn_predict_head(self.part, S, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
                                self.ylab if lab is not None else None, logp[s:s + b],
                                pred[s:s + b], conf)

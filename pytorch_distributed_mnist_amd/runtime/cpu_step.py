@@ -25,12 +25,14 @@ def _leaf_params(arena):
 
 
 def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, metrics_buf,
-                   dropout=None, dataset_index=None, epoch=None, lr=None, label_smoothing=0.0):
+                   dropout=None, dataset_index=None, epoch=None, lr=None, label_smoothing=0.0,
+                   ema=None):
     """dropout (a data.dropout.DropoutSpec, CNN): the hidden units of the batch's samples
     `dataset_index` are masked by their (seed, epoch, sample, unit) draws.  lr: this step's
     scheduled learning rate (optim/schedule.py), set on the optimizer before its step.
     label_smoothing (E in 0..1): the criterion's targets are (1 - E) onehot + E / 10, and the
-    loss added to the metrics is the smoothed one."""
+    loss added to the metrics is the smoothed one.  ema (an optim.ema.WeightEma): the averaged
+    weights take in the step's updated weights, ema += w (p - ema), after the optimizer."""
     x = normalize_reference(images_u8)
     mult = None
     if dropout is not None:
@@ -67,6 +69,8 @@ def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, met
             frozen = [(start, own[0]), (own[1], start + ws * count)]
             optimizer.step_cpu(grad_scale=reducer.grad_scale, frozen=frozen)
             reducer.gather(arena.params[start:start + ws * count])
+        if ema is not None:
+            ema.update_cpu(arena.params)
         bsz = images_u8.shape[0]
         correct = logits.argmax(dim=1).eq(labels).sum().item()
         metrics_buf[0] += loss.item() * bsz

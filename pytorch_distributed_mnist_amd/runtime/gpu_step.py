@@ -14,6 +14,9 @@ With a learning-rate schedule installed (optim/schedule.py), the launch that adv
 the optimizer-step counter also copies the step's rate from the run's table into the
 optimizer's lr word: lr and the step count travel together, to the same readers.
 
+With the weight average on (optim/ema.py) every chain below ends in one more launch,
+ema_update, which only reads the optimizer-step counter.
+
 Linear (reference Net, fp32):  lin_train -> [lin_reduce -> all-reduce] -> optim
 CNN (bf16):  cnn_fwd -> fc1_fwd -> cnn_head -> fc1_bwd -> [all-reduce bucket 0]
              -> cnn_bwd -> conv_reduce -> [all-reduce bucket 1] -> optim
@@ -26,6 +29,7 @@ import os
 import torch
 
 from ..ops import _ext
+from ..optim.ema import ema_weight
 from .. import knobs
 
 
@@ -108,6 +112,14 @@ class GpuStepBase:
         # step; begin_epoch puts it at epoch * spe when the device holds something else
         # (_sched_dev is the host's view of the device word, as _dev_step)
         self._install_schedule(getattr(prog, "schedule", None))
+        # exponential moving average of the weights (optim/ema.py): ema_update is the last
+        # launch of every step (launch_ema).  With the warmup on it computes the update's
+        # index from the optimizer-step word plus _ema_off, the host's count of updates minus
+        # the word's value (both move on by one per step, so the offset holds until either is
+        # set anew: a resume, the start-up check's restore); the offset is a kernel argument,
+        # baked into the graphs, which are re-captured when it changes (_ema_sync)
+        self.ema = getattr(prog, "ema", None)
+        self._ema_off = None
         self._epoch_start = 0
         self._gather_stream = None       # stream of the ahead-of-time gathers
         self._ring = None                # pinned staging buffers of the epoch orders
@@ -402,6 +414,7 @@ class GpuStepBase:
         when replayed."""
         if not self.use_graphs:
             return
+        self._ema_sync()                 # (the graphs bake the EMA launch's offset in)
         for n, ph, ci, co in self._variants(B, sizes or self.GRAPH_SIZES):
             g = self._graph(B, n, ph, ci, co)
             try:
@@ -422,6 +435,7 @@ class GpuStepBase:
             raise RuntimeError(f"{n} steps from global step {self._sched_dev} run past the "
                                f"learning-rate schedule's {self.schedule.total} steps "
                                f"({self.schedule.epochs} epochs of {self.schedule.spe})")
+        self._ema_sync()
         if self.use_graphs:
             plan = self._plan(B, n)
             if self.collective_outside():
@@ -451,6 +465,40 @@ class GpuStepBase:
             self._dev_step += n
         if self.schedule is not None:
             self._sched_dev += n
+        if self.ema is not None:
+            self.ema.updates += n
+
+    def _ema_sync(self) -> None:
+        """Before steps are queued: make the offset the EMA launch adds to the optimizer-step
+        word current (never inside a capture)."""
+        if self.ema is None:
+            return
+        if self._dev_step is None:       # nobody has put the host's step count on the device
+            self.opt.sync_step()
+            self._dev_step = self.opt.step_count
+        off = self.ema.updates - self._dev_step
+        if off != self._ema_off:
+            self._ema_off = off
+            if self.ema.spec.warmup:     # (without it the kernel does not read the offset)
+                self.graphs.clear()
+
+    def launch_ema(self) -> None:
+        """The step's last launch with the weight average on: ema += w (params - ema) over the
+        whole arena, behind the launch that completed the step's weight update."""
+        ema = self.ema
+        if ema is None:
+            return
+        sp = ema.spec
+        self.C.ema_update(self.arena.params, ema.params, self.arena.spec.total,
+                          ema_weight(sp.decay), sp.warmup, sp.decay, self.opt._step_dev,
+                          self._ema_off)
+
+    def weight_set(self, arena):
+        """What evaluate() / predict() read of a weight arena other than the training one (the
+        averaged weights): the name views and whatever compute copies the forward kernels
+        take, derived here, outside any capture.  The training weights, their copies and the
+        step phase are not involved."""
+        raise NotImplementedError
 
     def train_step(self, B: int) -> None:
         self.train_steps(B, 1)
@@ -479,6 +527,7 @@ class GpuStepBase:
             self.reducer.begin(n, self.collective_channels(), self.collective_wide(B))
         for _ in range(n):
             self._train_impl(B)
+            self.launch_ema()
             self.phase = (self.phase + 1) % self.phase_period
         if streamed:
             self.reducer.end()
@@ -646,11 +695,15 @@ class LinearStep(GpuStepBase):
         red.finalize()
         self.launch_optimizer()
 
-    def evaluate(self) -> None:
-        self.C.lin_eval(self.test_images, self.test_labels, self.W, self.b,
-                        self.metrics.eval_view())
+    def weight_set(self, arena):
+        return arena.param("fc.weight"), arena.param("fc.bias")
 
-    def predict(self, images_u8, labels=None):
+    def evaluate(self, ws=None) -> None:
+        W, b = (self.W, self.b) if ws is None else ws
+        self.C.lin_eval(self.test_images, self.test_labels, W, b, self.metrics.eval_view())
+
+    def predict(self, images_u8, labels=None, ws=None):
+        W, b = (self.W, self.b) if ws is None else ws
         images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
-        self.C.lin_predict(images, lab, self.W, self.b, logp, pred, conf)
+        self.C.lin_predict(images, lab, W, b, logp, pred, conf)
         return logp, pred, conf

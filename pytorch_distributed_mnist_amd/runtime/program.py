@@ -25,6 +25,7 @@ from ..data.augment import AugmentSpec, augment_batch
 from ..data.dropout import DropoutSpec
 from ..data.mnist import image_rows, label_vector
 from ..data.sampler import batch_bounds
+from ..optim.ema import EmaSpec, WeightEma
 from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
 from .cpu_step import eval_step_cpu, predict_step_cpu, train_step_cpu
@@ -52,8 +53,15 @@ class TrainProgram:
                  structure: Optional[StepStructure] = None,
                  augment: Optional[AugmentSpec] = None,
                  dropout: Optional[DropoutSpec] = None,
-                 schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0):
+                 schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
+                 ema: Optional[WeightEma] = None):
         self.model = model
+        # exponential moving average of the weights (optim/ema.py): a second flat buffer that
+        # takes in every step's whole weights after the step's update -- on the GPU the last
+        # launch of the step, inside the graphs, on the CPU after optimizer.step().  Training
+        # never reads it; evaluate() and predict() use it by default when it is on.  None: off,
+        # and nothing changes.
+        self.ema = ema
         # label smoothing (--label-smoothing E in 0..1): the training steps' targets are
         # (1 - E) onehot + E / 10, as torch's F.cross_entropy(..., label_smoothing=E) -- on the
         # GPU inside the head kernels, on the CPU in the criterion.  The training loss is the
@@ -174,7 +182,7 @@ class TrainProgram:
                                self.train_split.labels[idx], self.reducer, self.optimizer, buf,
                                dropout=self.dropout, dataset_index=idx, epoch=self._epoch,
                                lr=None if table is None else float(table[g0 + i]),
-                               label_smoothing=self.label_smoothing)
+                               label_smoothing=self.label_smoothing, ema=self.ema)
         return self.metrics.read(DeviceMetrics.TRAIN)
 
     def set_schedule(self, schedule: Optional[ScheduleSpec]) -> None:
@@ -198,6 +206,9 @@ class TrainProgram:
 
     def shard_unsupported_reason(self):
         """None when the fc1 update can be sharded here, else why not (for the user)."""
+        if self.ema is not None:
+            return ("the weight average (--ema-decay) takes in every step's whole weights on "
+                    "every rank")
         if self.model != "cnn":
             return f"the {self.model} model has no fc1 layer to shard"
         if self.gpu is not None:
@@ -265,28 +276,43 @@ class TrainProgram:
         """Run ``n`` full steps from the current counter (bench helper; GPU only)."""
         self.gpu.train_steps(bsz or self.batch_size, n)
 
+    def _eval_arena(self, average: Optional[bool]):
+        """The arena evaluate() / predict() read: the averaged weights when `average` (None:
+        whenever the average is on), else the training weights."""
+        if average is None:
+            average = self.ema is not None
+        if not average:
+            return self.arena
+        if self.ema is None:
+            raise ValueError("this program keeps no weight average (ema=None)")
+        return self.ema.arena
+
     @torch.no_grad()
-    def evaluate(self):
-        """Full, unsharded test-set pass on every rank (reference :99-116, :142-149)."""
+    def evaluate(self, average: Optional[bool] = None):
+        """Full, unsharded test-set pass on every rank (reference :99-116, :142-149).  With the
+        weight average on it evaluates the averaged weights (average=False: the training
+        weights); neither the training weights nor any state of the step is touched."""
         self.metrics.reset(DeviceMetrics.EVAL)
         n = len(self.test_split)
+        arena = self._eval_arena(average)
         if self.gpu is not None:
-            self.gpu.evaluate()
+            self.gpu.evaluate(None if arena is self.arena else self.gpu.weight_set(arena))
             if self.sync_fn is not None:
                 self.sync_fn("evaluation")
         else:
             buf = self.metrics.buf[3:6]
             for start, size in batch_bounds(n, self.eval_batch):
-                eval_step_cpu(self.model, self.arena, self.test_split.images[start:start + size],
+                eval_step_cpu(self.model, arena, self.test_split.images[start:start + size],
                               self.test_split.labels[start:start + size], buf)
         return self.metrics.read(DeviceMetrics.EVAL)
 
     @torch.no_grad()
-    def predict(self, images=None, labels=None) -> Prediction:
+    def predict(self, images=None, labels=None, average: Optional[bool] = None) -> Prediction:
         """Per-sample predictions of the current weights: for ``images`` (uint8 [N, 28, 28] or
         [N, 784], torch or NumPy, any N >= 1; ``labels`` optional), or with no arguments for the
         test split and its labels.  Runs evaluate()'s forward; the metric accumulators are not
-        touched."""
+        touched.  ``average``: as evaluate()'s."""
+        arena = self._eval_arena(average)
         if images is None:
             if labels is not None:
                 raise ValueError("labels without images")
@@ -299,12 +325,13 @@ class TrainProgram:
             if labels is not None:
                 labels = label_vector(labels, images.shape[0])
         if self.gpu is not None:
-            logp, pred, conf = self.gpu.predict(images, labels)
+            logp, pred, conf = self.gpu.predict(
+                images, labels, None if arena is self.arena else self.gpu.weight_set(arena))
             if self.sync_fn is not None:
                 self.sync_fn("prediction")
             return Prediction(logp.cpu(), pred.cpu().to(torch.int64),
                               None if conf is None else conf.cpu())
-        outs = [predict_step_cpu(self.model, self.arena, images[start:start + size],
+        outs = [predict_step_cpu(self.model, arena, images[start:start + size],
                                  None if labels is None else labels[start:start + size])
                 for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)]
         return Prediction(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
@@ -317,7 +344,8 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                         comm=None, force_comm: bool = False, transport: str | None = None,
                         augment: Optional[AugmentSpec] = None,
                         dropout: Optional[DropoutSpec] = None,
-                        schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0):
+                        schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
+                        ema: Optional[EmaSpec] = None):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -340,4 +368,5 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                           transport=transport)
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
                         use_graphs=use_graphs, augment=augment, dropout=dropout,
-                        schedule=schedule, label_smoothing=label_smoothing)
+                        schedule=schedule, label_smoothing=label_smoothing,
+                        ema=None if ema is None else WeightEma(ema, arena))

@@ -6,6 +6,9 @@ Format (reference ``multi_proc_single_gpu.py:249-271``, verified in SURVEY.md §
 'optimizer': torch-optimizer state_dict})`` written by rank 0 every epoch, plus a
 byte copy ``model_best.pth.tar`` when the test accuracy improved.
 
+With ``--ema-decay`` two keys are added, ``ema_state_dict`` and ``ema_updates`` (``make_state``);
+without it the dictionary has exactly the four above.
+
 Differences (deliberate, format-invisible): the write is atomic (temp file +
 ``os.replace``) so a crash never leaves a truncated checkpoint, tensors are
 saved on the CPU (loadable anywhere, still accepted by the reference's
@@ -60,10 +63,17 @@ def load_checkpoint(path: str, map_location="cpu") -> dict:
     return torch.load(path, map_location=map_location, weights_only=True)
 
 
-def make_state(epoch_done: int, arena, best_acc: float, optimizer) -> dict:
-    return {
+def make_state(epoch_done: int, arena, best_acc: float, optimizer, ema=None) -> dict:
+    """The reference's four keys; with a weight average (optim.ema.WeightEma) also
+    ``ema_state_dict`` (the names of ``state_dict``) and ``ema_updates`` (int).  ``state_dict``
+    always holds the training weights, so any checkpoint resumes anywhere."""
+    state = {
         "epoch": epoch_done,
         "state_dict": arena.state_dict(prefix="module."),
         "best_acc": best_acc,
         "optimizer": optimizer.state_dict(),
     }
+    if ema is not None:
+        state["ema_state_dict"] = ema.state_dict()
+        state["ema_updates"] = int(ema.updates)
+    return state

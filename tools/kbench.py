@@ -62,7 +62,14 @@ def main():
       head = lambda **kw: C.cnn_head(st.part, S, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
                                      st.ylab, True, st.dh, st.dht, ldt, st.head_slab,
                                      st.metrics.train_view(), None, c1, **kw)
+      # the weight average's launch (ema.hip) over the arena into a scratch average, with plain
+      # and with nontemporal accesses of the average
+      avg = torch.zeros_like(p.arena.params)
+      ema = lambda nt: C.ema_update(p.arena.params, avg, p.arena.spec.total, 0.0009765625, False,
+                                    0.9990234375, c1, 0, nt=nt)
       ks = {
+          "ema": lambda: ema(False),
+          "ema_nt": lambda: ema(True),
           "cnn_fwd": lambda: C.cnn_fwd(st.ep_images.view(-1, 784), st.ep_labels, None, z, B, B,
                                        P["conv1.weight"], P["conv1.bias"], st.w2, P["conv2.bias"],
                                        st.pool, st.pmask, *st.fwd_outputs(B)),
@@ -102,7 +109,7 @@ def main():
       for name, fn in ks.items():
           us = timeit(fn)
           if name not in ("cnn_head_dropout", "cnn_head_smooth", "cnn_head_step",
-                          "cnn_head_sched"):                                        # variants
+                          "cnn_head_sched", "ema", "ema_nt"):            # variants, opt-in launches
               tot += us
           line.append(f"{name}={us:.1f}")
       st.ctr.zero_()   # each step advances the data counter (rows are clamped past the epoch)

@@ -254,11 +254,13 @@ void gather_epoch(at::Tensor images, at::Tensor labels, at::Tensor idx, at::Tens
 // gather_epoch with the train-time augmentation (kernels/augment.hip): the same arguments and
 // contract, plus the Q14 tables cosq / sinq (int32 [1024]) and invz (int32 [64]) on the device,
 // the shift range in pixels (0..8), the epoch and the 64-bit augmentation seed.
-void gather_epoch_augment(at::Tensor images, at::Tensor labels, at::Tensor idx,
-                          at::Tensor out_images, at::Tensor out_labels,
-                          c10::optional<at::Tensor> ctr, c10::optional<at::Tensor> step,
-                          int64_t step_value, int64_t max_wgs, at::Tensor cosq, at::Tensor sinq,
-                          at::Tensor invz, int64_t shift, int64_t epoch, uint64_t seed) {
+// elastic_q < 0: the affine kernel; 0..768: the elastic kernel (gather_epoch_elastic below).
+static void gather_epoch_augment_impl(at::Tensor images, at::Tensor labels, at::Tensor idx,
+                                      at::Tensor out_images, at::Tensor out_labels,
+                                      c10::optional<at::Tensor> ctr, c10::optional<at::Tensor> step,
+                                      int64_t step_value, int64_t max_wgs, at::Tensor cosq,
+                                      at::Tensor sinq, at::Tensor invz, int64_t shift,
+                                      int64_t epoch, uint64_t seed, int64_t elastic_q) {
   c10::DeviceGuard g(images.device());
   need(images, at::kByte, "images");
   need(labels, at::kInt, "labels");
@@ -302,12 +304,44 @@ void gather_epoch_augment(at::Tensor images, at::Tensor labels, at::Tensor idx,
     need(*step, at::kLong, "step");
     sp = ptr<int64_t>(*step);
   }
-  launch_gather_epoch_augment(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), ip, (int)n,
-                              (int)images.size(0), out_images.data_ptr<uint8_t>(),
-                              out_labels.data_ptr<int32_t>(), cp, nctr, sp, step_value,
-                              (int)max_wgs, cosq.data_ptr<int32_t>(), sinq.data_ptr<int32_t>(),
-                              invz.data_ptr<int32_t>(), (int)shift, (uint32_t)epoch, seed,
-                              cur_stream(images));
+  if (elastic_q < 0) {
+    launch_gather_epoch_augment(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), ip, (int)n,
+                                (int)images.size(0), out_images.data_ptr<uint8_t>(),
+                                out_labels.data_ptr<int32_t>(), cp, nctr, sp, step_value,
+                                (int)max_wgs, cosq.data_ptr<int32_t>(), sinq.data_ptr<int32_t>(),
+                                invz.data_ptr<int32_t>(), (int)shift, (uint32_t)epoch, seed,
+                                cur_stream(images));
+  } else {
+    launch_gather_epoch_elastic(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), ip, (int)n,
+                                (int)images.size(0), out_images.data_ptr<uint8_t>(),
+                                out_labels.data_ptr<int32_t>(), cp, nctr, sp, step_value,
+                                (int)max_wgs, cosq.data_ptr<int32_t>(), sinq.data_ptr<int32_t>(),
+                                invz.data_ptr<int32_t>(), (int)shift, (uint32_t)epoch, seed,
+                                (int)elastic_q, cur_stream(images));
+  }
+}
+
+void gather_epoch_augment(at::Tensor images, at::Tensor labels, at::Tensor idx,
+                          at::Tensor out_images, at::Tensor out_labels,
+                          c10::optional<at::Tensor> ctr, c10::optional<at::Tensor> step,
+                          int64_t step_value, int64_t max_wgs, at::Tensor cosq, at::Tensor sinq,
+                          at::Tensor invz, int64_t shift, int64_t epoch, uint64_t seed) {
+  gather_epoch_augment_impl(images, labels, idx, out_images, out_labels, ctr, step, step_value,
+                            max_wgs, cosq, sinq, invz, shift, epoch, seed, -1);
+}
+
+// gather_epoch_augment plus elastic distortion (--aug-elastic): elastic_q = rint(256 A), the
+// control displacements' range in 1/256 px (0..768).  Always the elastic kernel, at
+// elastic_q = 0 too (its output is then gather_epoch_augment's, which a test compares).
+void gather_epoch_elastic(at::Tensor images, at::Tensor labels, at::Tensor idx,
+                          at::Tensor out_images, at::Tensor out_labels,
+                          c10::optional<at::Tensor> ctr, c10::optional<at::Tensor> step,
+                          int64_t step_value, int64_t max_wgs, at::Tensor cosq, at::Tensor sinq,
+                          at::Tensor invz, int64_t shift, int64_t epoch, uint64_t seed,
+                          int64_t elastic_q) {
+  TORCH_CHECK(elastic_q >= 0 && elastic_q <= 768, "elastic_q must be in 0..768, got ", elastic_q);
+  gather_epoch_augment_impl(images, labels, idx, out_images, out_labels, ctr, step, step_value,
+                            max_wgs, cosq, sinq, invz, shift, epoch, seed, elastic_q);
 }
 
 // ------------------------------------------------------------------ optimizer
@@ -1201,6 +1235,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0,
         py::arg("cosq"), py::arg("sinq"), py::arg("invz"), py::arg("shift"), py::arg("epoch"),
         py::arg("seed"));
+  m.def("gather_epoch_elastic", &gather_epoch_elastic, py::arg("images"), py::arg("labels"),
+        py::arg("idx"), py::arg("out_images"), py::arg("out_labels"), py::arg("ctr") = py::none(),
+        py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0,
+        py::arg("cosq"), py::arg("sinq"), py::arg("invz"), py::arg("shift"), py::arg("epoch"),
+        py::arg("seed"), py::arg("elastic_q"));
   m.def("xgmi_wait", &xgmi_wait);
   m.def("debug_spin", &debug_spin, py::arg("seconds"));
   m.attr("CNN_HEAD_ROWS") = CNN_HEAD_ROWS;

@@ -77,6 +77,17 @@ void launch_gather_epoch_augment(const uint8_t* images, const int32_t* labels, c
                                  int max_wgs, const int32_t* cosq, const int32_t* sinq,
                                  const int32_t* invz, int shift, uint32_t epoch, uint64_t seed,
                                  hipStream_t st);
+// The augmenting gather plus elastic distortion (gather_epoch_elastic_kernel): a quadratic
+// B-spline displacement over 6 x 6 control points per image, each uniform in
+// [-elastic_q, elastic_q] / 256 pixels (elastic_q in 0..768), drawn with counter (dataset
+// index, epoch, 2, point).  Always launches the elastic kernel; elastic_q = 0 gives
+// launch_gather_epoch_augment's bits.
+void launch_gather_epoch_elastic(const uint8_t* images, const int32_t* labels, const int32_t* idx,
+                                 int n, int nimg, uint8_t* out_images, int32_t* out_labels,
+                                 int64_t* ctr, int nctr, int64_t* step, int64_t step_value,
+                                 int max_wgs, const int32_t* cosq, const int32_t* sinq,
+                                 const int32_t* invz, int shift, uint32_t epoch, uint64_t seed,
+                                 int elastic_q, hipStream_t st);
 
 // ---------------------------------------------------------------- optimizer
 constexpr int OPT_ADAM = 0;

@@ -10,8 +10,8 @@ Additions are opt-in and default to the reference's behaviour:
 :192-194), ``--dtype {fp32,bf16}``, ``--synthetic``/``--synthetic-size``,
 ``--device``, ``--no-graphs``, ``--checkpoint-dir``, ``--timeout``, ``--perf``,
 ``--rank-prefix``, ``--predict-out`` (with ``--evaluate``) and the train-time augmentation
-``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-seed``, dropout on the CNN's
-hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
+``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-elastic`` / ``--aug-seed``,
+dropout on the CNN's hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
 ``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
 ``--label-smoothing``, and the exponential moving average of the weights, ``--ema-decay`` /
 ``--ema-warmup``.
@@ -143,6 +143,11 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument('--aug-zoom', metavar='F', type=_ranged(float, 0.0, 0.5),
                    default=argparse.SUPPRESS,
                    help='train-time augmentation: random zoom by a factor in 1 -/+ F (0..0.5)')
+    g.add_argument('--aug-elastic', metavar='A', type=_ranged(float, 0.0, 3.0),
+                   default=argparse.SUPPRESS,
+                   help='train-time augmentation: elastic distortion, a smooth random '
+                        'displacement field per sample and epoch whose control points move by '
+                        'up to A pixels (0..3)')
     g.add_argument('--aug-seed', metavar='N', type=_ranged(int, 0, 2 ** 64 - 1),
                    default=argparse.SUPPRESS,
                    help='seed of the augmentation draws (default: --seed if given, else 0); a '

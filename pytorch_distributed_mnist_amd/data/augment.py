@@ -1,4 +1,5 @@
-"""Train-time augmentation: a small random shift, rotation and zoom per sample and epoch.
+"""Train-time augmentation: a small random shift, rotation and zoom per sample and epoch, and
+an elastic distortion (Simard et al. 2003).
 
 The transform is integer-only, so the GPU kernel (``csrc/kernels/augment.hip``), this NumPy
 implementation (the CPU path's, and the kernel's oracle) and the tests agree bit for bit.
@@ -30,6 +31,25 @@ Inverse map (every ``>>`` is an arithmetic shift, i.e. floor)::
 
 with ``p`` zero outside the 28 x 28 image.  Everything fits int32.  S = R = Z = 0 is exactly
 the identity.  Labels are never changed; evaluation and prediction are never augmented.
+
+Elastic distortion (``elastic`` = A pixels, 0..3; E = rint(256 A), in 1/256 px) adds a smooth
+per-sample displacement (ex, ey) to SX and SY.  A 6 x 6 grid of control displacements at a
+spacing of 8 pixels, control point q = 6 cy + cx drawn with counter
+``(dataset_index, epoch, 2, q)`` (word 2: 0 is the draw above, 1 is dropout's)::
+
+    gx[q] = (((r0 >> 16) (2E+1)) >> 16) - E      gy[q] likewise from r1: uniform in [-E, E]
+
+and a uniform quadratic B-spline over the 3 x 3 control points around the output pixel, exact
+in integers because a cell is 16 half-pixels::
+
+    hx = 2x + 1, cx0 = hx >> 4 (0..3), f = hx & 15;  hy, cy0, g likewise from y
+    wx = [(16-f)^2, 256 + 32f - 2f^2, f^2]       (sums to 512)      wy the same in g
+    ex = (sum_{b,a in 0..2} wy[b] wx[a] gx[6 (cy0+b) + cx0+a] + 2^17) >> 18;  ey with gy
+    SX += ex, SY += ey
+
+The sums are at most 2^18 * 768; |ex| <= E; neighbouring pixels differ by at most E/4 + 1, so
+with A <= 3 the map never folds (256 + the difference >= 63).  E = 0 gives ex = ey = 0.  The
+grid spacing is fixed: a second one would need more control points than a wave has lanes.
 """
 from __future__ import annotations
 
@@ -41,6 +61,8 @@ import torch
 MAX_SHIFT = 8
 MAX_ROTATE = 45.0
 MAX_ZOOM = 0.5
+MAX_ELASTIC = 3.0
+ELASTIC_GRID = 6                  # control points per axis, at a spacing of 8 pixels
 ANGLE_LEVELS = 1024
 ZOOM_LEVELS = 64
 
@@ -52,11 +74,14 @@ _MASK32 = 0xFFFFFFFF
 @dataclass(frozen=True)
 class AugmentSpec:
     """Ranges of the per-sample transform: ``shift`` pixels (0..8), ``rotate`` degrees
-    (0..45), ``zoom`` fraction (0..0.5), and the 64-bit ``seed`` of the Philox key."""
+    (0..45), ``zoom`` fraction (0..0.5), the 64-bit ``seed`` of the Philox key, and
+    ``elastic`` pixels (0..3), the range of the elastic field's control displacements (last,
+    behind ``seed``: the first four are given positionally)."""
     shift: int = 0
     rotate: float = 0.0
     zoom: float = 0.0
     seed: int = 0
+    elastic: float = 0.0
 
     def __post_init__(self):
         if int(self.shift) != self.shift or not 0 <= self.shift <= MAX_SHIFT:
@@ -65,14 +90,22 @@ class AugmentSpec:
             raise ValueError(f"rotate must be in 0..{MAX_ROTATE} degrees, got {self.rotate!r}")
         if not 0.0 <= self.zoom <= MAX_ZOOM:
             raise ValueError(f"zoom must be in 0..{MAX_ZOOM}, got {self.zoom!r}")
+        if not 0.0 <= self.elastic <= MAX_ELASTIC:
+            raise ValueError(f"elastic must be in 0..{MAX_ELASTIC} pixels, got {self.elastic!r}")
         object.__setattr__(self, "shift", int(self.shift))
         object.__setattr__(self, "rotate", float(self.rotate))
         object.__setattr__(self, "zoom", float(self.zoom))
         object.__setattr__(self, "seed", int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+        object.__setattr__(self, "elastic", float(self.elastic))
 
     @property
     def enabled(self) -> bool:
-        return self.shift > 0 or self.rotate > 0.0 or self.zoom > 0.0
+        return self.shift > 0 or self.rotate > 0.0 or self.zoom > 0.0 or self.elastic > 0.0
+
+    @property
+    def elastic_q(self) -> int:
+        """E: the elastic range in 1/256 px, 0..768."""
+        return int(np.rint(256.0 * self.elastic))
 
     @property
     def key(self):
@@ -119,6 +152,45 @@ def draw(dataset_index, epoch: int, spec: AugmentSpec):
     return r[:, 0] >> 22, r[:, 1] >> 26, r[:, 2] % span - spec.shift, r[:, 3] % span - spec.shift
 
 
+def elastic_controls(dataset_index, epoch: int, spec: AugmentSpec):
+    """The elastic field's control displacements (gx, gy), int64 [N, 6, 6] each (indexed
+    [sample, cy, cx]), in 1/256 px."""
+    idx = np.asarray(dataset_index, dtype=np.int64).reshape(-1)
+    q = ELASTIC_GRID * ELASTIC_GRID
+    ctr = np.zeros((idx.shape[0], q, 4), dtype=np.uint64)
+    ctr[:, :, 0] = (idx.astype(np.uint64) & _MASK32)[:, None]
+    ctr[:, :, 1] = int(epoch) & _MASK32
+    ctr[:, :, 2] = 2
+    ctr[:, :, 3] = np.arange(q, dtype=np.uint64)[None, :]
+    r = philox4x32_10(ctr, np.array(spec.key, dtype=np.uint64)).astype(np.int64)
+    e = spec.elastic_q
+    g = (((r[..., :2] >> 16) * (2 * e + 1)) >> 16) - e
+    shape = (idx.shape[0], ELASTIC_GRID, ELASTIC_GRID)
+    return g[..., 0].reshape(shape), g[..., 1].reshape(shape)
+
+
+def _spline_weights(h):
+    """Quadratic B-spline weights of the half-pixel coordinate ``h`` = 2x + 1 (int64 [28]):
+    the first cell index [28] and the three weights [3, 28], which sum to 512."""
+    f = h & 15
+    return h >> 4, np.stack([(16 - f) ** 2, 256 + 32 * f - 2 * f * f, f * f])
+
+
+def elastic_field(dataset_index, epoch: int, spec: AugmentSpec):
+    """The elastic displacements (ex, ey), int64 [N, 784] each, in 1/256 px."""
+    gx, gy = elastic_controls(dataset_index, epoch, spec)
+    c0, w = _spline_weights(2 * np.arange(28, dtype=np.int64) + 1)
+    cols = c0[None, :] + np.arange(3)[:, None]                  # [3, 28] control index per tap
+
+    def field(g):
+        # along x, then along y: rows[n, cy, x], then out[n, y, x]; exact, so the order is free
+        rows = (g[:, :, cols] * w[None, None]).sum(axis=2)
+        out = (rows[:, cols, :] * w[None, :, :, None]).sum(axis=1)
+        return ((out + (1 << 17)) >> 18).reshape(g.shape[0], 784)
+
+    return field(gx), field(gy)
+
+
 def _u8_rows(images):
     a = images.numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
     if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != 784:
@@ -146,6 +218,9 @@ def augment_batch(images_u8, dataset_index, epoch: int, spec: AugmentSpec, table
     v = (2 * (pix // 28) - 27)[None, :]
     sx = ((A * u + B * v + 64) >> 7) + 3456 - 256 * dx[:, None]
     sy = ((-B * u + A * v + 64) >> 7) + 3456 - 256 * dy[:, None]
+    if spec.elastic > 0.0:
+        ex, ey = elastic_field(idx, epoch, spec)
+        sx, sy = sx + ex, sy + ey
     x0, fx, y0, fy = sx >> 8, sx & 255, sy >> 8, sy & 255
     rows = np.arange(n)[:, None]
 
@@ -168,5 +243,5 @@ def spec_from_args(args):
     seed = getattr(args, "aug_seed", None)
     if seed is None:
         seed = args.seed if getattr(args, "seed", None) is not None else 0
-    spec = AugmentSpec(shift, rotate, zoom, seed)
+    spec = AugmentSpec(shift, rotate, zoom, seed, getattr(args, "aug_elastic", 0.0))
     return spec if spec.enabled else None

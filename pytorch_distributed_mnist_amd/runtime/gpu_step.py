@@ -174,6 +174,17 @@ class GpuStepBase:
                                     # one workgroup per 64 rows (grid-striding ones taking
                                     # fewer CUs beside the steps measured no better)
                                     max_wgs=0)
+            elif self.augment.elastic > 0.0:
+                # --aug-elastic: the elastic twin of the augmenting gather (the same contract,
+                # plus the control displacements' range)
+                cosq, sinq, invz = self._aug_tables
+                self.C.gather_epoch_elastic(self.train_images, self.train_labels, buf[0],
+                                            self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
+                                            self.ep_labels[half * n:(half + 1) * n],
+                                            max_wgs=0, cosq=cosq, sinq=sinq, invz=invz,
+                                            shift=self.augment.shift, epoch=int(epoch),
+                                            seed=self.augment.seed,
+                                            elastic_q=self.augment.elastic_q)
             else:
                 cosq, sinq, invz = self._aug_tables
                 self.C.gather_epoch_augment(self.train_images, self.train_labels, buf[0],

@@ -1,5 +1,5 @@
 """GPU time of the epoch gathers at one rank's epoch (n = 60,000 by default): gather_epoch
-(data.hip) and gather_epoch_augment (augment.hip), on an otherwise idle GPU.
+(data.hip), gather_epoch_augment and gather_epoch_elastic (augment.hip), on an otherwise idle GPU.
 
     python tools/gather_bench.py [n]
 
@@ -70,6 +70,17 @@ def main():
         want = augment_batch(train.images[order[:k].long()], order[:k].long(), 1, spec)
         assert torch.equal(out_i[:k].cpu(), want), name
         print(f"gather_epoch_augment {name:30s} {us:8.1f} us")
+    for name, spec in (("elastic 2", AugmentSpec(0, 0.0, 0.0, 1, 2.0)),
+                       ("shift 2, rotate 10, zoom 0.1, el. 2", AugmentSpec(2, 10.0, 0.1, 1, 2.0))):
+        cosq, sinq, invz = (torch.from_numpy(t).cuda() for t in spec.tables())
+        fn = lambda: C.gather_epoch_elastic(images, labels, idx, out_i, out_l, None, None, 0, 0,
+                                            cosq, sinq, invz, spec.shift, 1, spec.seed,
+                                            spec.elastic_q)
+        us = timeit(fn)
+        k = min(n, 2048)
+        want = augment_batch(train.images[order[:k].long()], order[:k].long(), 1, spec)
+        assert torch.equal(out_i[:k].cpu(), want), name
+        print(f"gather_epoch_elastic {name:30s} {us:8.1f} us")
 
 
 if __name__ == "__main__":

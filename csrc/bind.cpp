@@ -260,7 +260,9 @@ static void gather_epoch_augment_impl(at::Tensor images, at::Tensor labels, at::
                                       c10::optional<at::Tensor> ctr, c10::optional<at::Tensor> step,
                                       int64_t step_value, int64_t max_wgs, at::Tensor cosq,
                                       at::Tensor sinq, at::Tensor invz, int64_t shift,
-                                      int64_t epoch, uint64_t seed, int64_t elastic_q) {
+                                      int64_t epoch, uint64_t seed, int64_t elastic_q,
+                                      c10::optional<at::Tensor> qt = c10::nullopt,
+                                      int64_t ntrain = 0, uint64_t mixup_seed = 0) {
   c10::DeviceGuard g(images.device());
   need(images, at::kByte, "images");
   need(labels, at::kInt, "labels");
@@ -304,7 +306,20 @@ static void gather_epoch_augment_impl(at::Tensor images, at::Tensor labels, at::
     need(*step, at::kLong, "step");
     sp = ptr<int64_t>(*step);
   }
-  if (elastic_q < 0) {
+  if (qt.has_value()) {
+    // mixup (gather_epoch_mixup below): the partner is one of the first ntrain rows of `images`
+    need(*qt, at::kInt, "qt");
+    need_numel(*qt, 1024, "qt");
+    TORCH_CHECK(ntrain >= 1 && ntrain <= images.size(0), "ntrain must be in 1..", images.size(0),
+                " (the rows of images), got ", ntrain);
+    launch_gather_epoch_mixup(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), ip, (int)n,
+                              (int)images.size(0), out_images.data_ptr<uint8_t>(),
+                              out_labels.data_ptr<int32_t>(), cp, nctr, sp, step_value,
+                              (int)max_wgs, cosq.data_ptr<int32_t>(), sinq.data_ptr<int32_t>(),
+                              invz.data_ptr<int32_t>(), (int)shift, (uint32_t)epoch, seed,
+                              (int)elastic_q, qt->data_ptr<int32_t>(), (int)ntrain, mixup_seed,
+                              cur_stream(images));
+  } else if (elastic_q < 0) {
     launch_gather_epoch_augment(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), ip, (int)n,
                                 (int)images.size(0), out_images.data_ptr<uint8_t>(),
                                 out_labels.data_ptr<int32_t>(), cp, nctr, sp, step_value,
@@ -342,6 +357,22 @@ void gather_epoch_elastic(at::Tensor images, at::Tensor labels, at::Tensor idx,
   TORCH_CHECK(elastic_q >= 0 && elastic_q <= 768, "elastic_q must be in 0..768, got ", elastic_q);
   gather_epoch_augment_impl(images, labels, idx, out_images, out_labels, ctr, step, step_value,
                             max_wgs, cosq, sinq, invz, shift, epoch, seed, elastic_q);
+}
+
+// gather_epoch_elastic with mixup (--mixup; kernels.h launch_gather_epoch_mixup): plus qt (int32
+// [1024] on the device, the folded Beta quantiles in 1/256), ntrain (partners are drawn from the
+// first ntrain rows of images: the training set) and the 64-bit mixup seed.  Always the mixup
+// kernel; identity tables, shift 0 and elastic_q = 0 give the plain mixed gather.
+void gather_epoch_mixup(at::Tensor images, at::Tensor labels, at::Tensor idx, at::Tensor out_images,
+                        at::Tensor out_labels, c10::optional<at::Tensor> ctr,
+                        c10::optional<at::Tensor> step, int64_t step_value, int64_t max_wgs,
+                        at::Tensor cosq, at::Tensor sinq, at::Tensor invz, int64_t shift,
+                        int64_t epoch, uint64_t seed, int64_t elastic_q, at::Tensor qt,
+                        int64_t ntrain, uint64_t mixup_seed) {
+  TORCH_CHECK(elastic_q >= 0 && elastic_q <= 768, "elastic_q must be in 0..768, got ", elastic_q);
+  gather_epoch_augment_impl(images, labels, idx, out_images, out_labels, ctr, step, step_value,
+                            max_wgs, cosq, sinq, invz, shift, epoch, seed, elastic_q, qt, ntrain,
+                            mixup_seed);
 }
 
 // ------------------------------------------------------------------ optimizer
@@ -823,6 +854,59 @@ at::Tensor dropout_mask_rows(at::Tensor ylab, at::Tensor epoch, uint64_t seed, i
   return out;
 }
 
+// The mixup pair's arguments (kernels.h launch_cnn_head_mixup): the tagged training labels
+// (int32 [>= ntrain] on the device) and the quantile table (int32 [1024]).
+void check_mixup(const at::Tensor& train_labels, int64_t ntrain, const at::Tensor& qt) {
+  need(train_labels, at::kInt, "train_labels");
+  TORCH_CHECK(ntrain >= 1 && ntrain <= train_labels.numel() && ntrain <= (1LL << 27),
+              "ntrain must be in 1..", train_labels.numel(), " (the training labels), got ", ntrain);
+  need(qt, at::kInt, "qt");
+  need_numel(qt, 1024, "qt");
+}
+
+// cnn_head_dropout with mixup (kernels/cnn_head_mix.hip): its arguments and checks (T = 0,
+// scale = 1: no dropout), plus the tagged training labels, their count, the quantile table and
+// the 64-bit mixup seed.
+void cnn_head_mixup(at::Tensor part, int64_t splitk, int64_t B, at::Tensor bf1, at::Tensor wf2,
+                    at::Tensor bf2, at::Tensor ylab, c10::optional<at::Tensor> dh,
+                    c10::optional<at::Tensor> dht, int64_t ldt, c10::optional<at::Tensor> slab,
+                    at::Tensor metrics, c10::optional<at::Tensor> c0, c10::optional<at::Tensor> c1,
+                    c10::optional<at::Tensor> xg, c10::optional<at::Tensor> dh32, at::Tensor epoch,
+                    uint64_t seed, int64_t T, double scale, at::Tensor train_labels, int64_t ntrain,
+                    at::Tensor qt, uint64_t mixup_seed, c10::optional<py::tuple> lr_sched,
+                    double label_smoothing) {
+  c10::DeviceGuard g(part.device());
+  const HeadOut o = check_head(part, splitk, B, bf1, wf2, bf2, ylab, true, dh, dht, ldt, slab,
+                               metrics, dh32);
+  const uint32_t* pe = check_dropout(epoch, T);
+  TORCH_CHECK(scale >= 1.0 && scale <= 65536.0 / (65536.0 - DROPOUT_MAX_T) + 1e-6,
+              "scale must be 65536 / (65536 - T), got ", scale);
+  check_mixup(train_labels, ntrain, qt);
+  const float eps = check_smoothing(label_smoothing);
+  launch_cnn_head_mixup(part.data_ptr<float>(), (int)splitk, (int)B, bf1.data_ptr<float>(),
+                        wf2.data_ptr<float>(), bf2.data_ptr<float>(), ylab.data_ptr<int32_t>(),
+                        o.dh, o.dht, (int)ldt, o.slab, opt_i64(c0), opt_i64(c1), xg_step(xg),
+                        o.dh32, pe, seed, (uint32_t)T, (float)scale,
+                        train_labels.data_ptr<int32_t>(), (int)ntrain, qt.data_ptr<int32_t>(),
+                        mixup_seed, cur_stream(part), opt_lr_sched(lr_sched, opt_i64(c1)), eps);
+}
+
+// The pairs alone, for the rows of ylab (label | dataset index << 4): int32 [B, 3] = (j, q, y2).
+at::Tensor mixup_pairs_rows(at::Tensor ylab, at::Tensor epoch, uint64_t mixup_seed,
+                            at::Tensor train_labels, int64_t ntrain, at::Tensor qt) {
+  c10::DeviceGuard g(ylab.device());
+  need(ylab, at::kInt, "ylab");
+  TORCH_CHECK(ylab.dim() == 1 && ylab.numel() >= 1, "ylab must be [B >= 1]");
+  const uint32_t* pe = check_dropout(epoch, 0);
+  check_mixup(train_labels, ntrain, qt);
+  const int64_t B = ylab.numel();
+  at::Tensor out = at::empty({B, (int64_t)3}, ylab.options());
+  launch_mixup_pairs_rows(ylab.data_ptr<int32_t>(), (int)B, pe, train_labels.data_ptr<int32_t>(),
+                          (int)ntrain, qt.data_ptr<int32_t>(), mixup_seed, out.data_ptr<int32_t>(),
+                          cur_stream(ylab));
+  return out;
+}
+
 // ------------------------------------------------------------------ prediction
 // Outputs of the prediction heads (kernels.h): logp fp32 [>= B * 10], pred int32 [>= B];
 // confusion (int64 [10][10]) and metrics (fp64 [3]) are optional and need labels.
@@ -1240,6 +1324,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0,
         py::arg("cosq"), py::arg("sinq"), py::arg("invz"), py::arg("shift"), py::arg("epoch"),
         py::arg("seed"), py::arg("elastic_q"));
+  m.def("gather_epoch_mixup", &gather_epoch_mixup, py::arg("images"), py::arg("labels"),
+        py::arg("idx"), py::arg("out_images"), py::arg("out_labels"), py::arg("ctr") = py::none(),
+        py::arg("step") = py::none(), py::arg("step_value") = 0, py::arg("max_wgs") = 0,
+        py::arg("cosq"), py::arg("sinq"), py::arg("invz"), py::arg("shift"), py::arg("epoch"),
+        py::arg("seed"), py::arg("elastic_q"), py::arg("qt"), py::arg("ntrain"),
+        py::arg("mixup_seed"));
   m.def("xgmi_wait", &xgmi_wait);
   m.def("debug_spin", &debug_spin, py::arg("seconds"));
   m.attr("CNN_HEAD_ROWS") = CNN_HEAD_ROWS;
@@ -1274,6 +1364,15 @@ PYBIND11_MODULE(_C, m) {
         py::arg("label_smoothing"), py::arg("lr_sched") = py::none());
   m.def("dropout_mask_rows", &dropout_mask_rows, py::arg("ylab"), py::arg("epoch"),
         py::arg("seed"), py::arg("T"));
+  m.def("cnn_head_mixup", &cnn_head_mixup, py::arg("part"), py::arg("splitk"), py::arg("B"),
+        py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("dh"),
+        py::arg("dht"), py::arg("ldt"), py::arg("slab"), py::arg("metrics"), py::arg("c0"),
+        py::arg("c1"), py::arg("xg") = py::none(), py::arg("dh32") = py::none(), py::arg("epoch"),
+        py::arg("seed") = 0, py::arg("T") = 0, py::arg("scale") = 1.0, py::arg("train_labels"),
+        py::arg("ntrain"), py::arg("qt"), py::arg("mixup_seed"),
+        py::arg("lr_sched") = py::none(), py::arg("label_smoothing") = 0.0);
+  m.def("mixup_pairs_rows", &mixup_pairs_rows, py::arg("ylab"), py::arg("epoch"),
+        py::arg("mixup_seed"), py::arg("train_labels"), py::arg("ntrain"), py::arg("qt"));
   m.def("cnn_predict_head", &cnn_predict_head, py::arg("part"), py::arg("splitk"), py::arg("B"),
         py::arg("bf1"), py::arg("wf2"), py::arg("bf2"), py::arg("ylab"), py::arg("logp"),
         py::arg("pred"), py::arg("confusion") = py::none(), py::arg("metrics") = py::none());

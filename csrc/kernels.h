@@ -88,6 +88,19 @@ void launch_gather_epoch_elastic(const uint8_t* images, const int32_t* labels, c
                                  int max_wgs, const int32_t* cosq, const int32_t* sinq,
                                  const int32_t* invz, int shift, uint32_t epoch, uint64_t seed,
                                  int elastic_q, hipStream_t st);
+// The elastic gather with mixup (gather_epoch_mixup_kernel; docs/kernels.md "Mixup",
+// kernels/mixup.h): every source byte of image i is read as the blend (q a + (256 - q) b + 128)
+// >> 8 with its partner j's byte, (j, q) drawn with counter (i, epoch, 3, 0) and key
+// `mixup_seed`: j = (r0 * ntrain) >> 32, q = qt[r1 >> 22] (qt int32 [1024], 128..256).  The
+// transform is i's; labels are copied verbatim.  1 <= ntrain <= nimg.  Always launches the mixup
+// kernel; qt == 256 everywhere gives launch_gather_epoch_elastic's bits.
+void launch_gather_epoch_mixup(const uint8_t* images, const int32_t* labels, const int32_t* idx,
+                               int n, int nimg, uint8_t* out_images, int32_t* out_labels,
+                               int64_t* ctr, int nctr, int64_t* step, int64_t step_value,
+                               int max_wgs, const int32_t* cosq, const int32_t* sinq,
+                               const int32_t* invz, int shift, uint32_t epoch, uint64_t seed,
+                               int elastic_q, const int32_t* qt, int ntrain, uint64_t mixup_seed,
+                               hipStream_t st);
 
 // ---------------------------------------------------------------- optimizer
 constexpr int OPT_ADAM = 0;
@@ -299,6 +312,23 @@ void launch_cnn_head_dropout(const float* part, int splitk, int B, const float* 
 void launch_dropout_mask_rows(const int32_t* ylab, int B, const uint32_t* epoch, uint64_t seed,
                               uint32_t T, uint8_t* out, hipStream_t st);
 constexpr uint32_t DROPOUT_MAX_T = 58982;   // round(0.9 * 65536): p is accepted in [0, 0.9]
+// launch_cnn_head_dropout with mixup (cnn_head_mix.hip; docs/kernels.md "Mixup"): the row's
+// pair (j, q) is recomputed from its tagged label word and *epoch (kernels/mixup.h, key
+// `mixup_seed`), y2 = train_labels[j] & 15 (train_labels: the ntrain tagged training labels),
+// lambda = q / 256, and the target is lambda t(y) + (1 - lambda) t(y2), the loss column
+// lambda loss(y) + (1 - lambda) loss(y2); correct is against y.  T = 0, scale = 1: no dropout.
+// Everything else is launch_cnn_head_dropout's; qt == 256 everywhere gives its bits.
+void launch_cnn_head_mixup(const float* part, int splitk, int B, const float* bf1, const float* wf2,
+                           const float* bf2, const int32_t* ylab, __bf16* dh, __bf16* dht, int ldt,
+                           float* slab, int64_t* c0, int64_t* c1, unsigned* c2, float* dh32,
+                           const uint32_t* epoch, uint64_t seed, uint32_t T, float scale,
+                           const int32_t* train_labels, int ntrain, const int32_t* qt,
+                           uint64_t mixup_seed, hipStream_t st, LrSched ls = LrSched(),
+                           float label_smoothing = 0.f);
+// (j, q, y2) of B rows alone (int32 [B][3]), from the head's device function
+void launch_mixup_pairs_rows(const int32_t* ylab, int B, const uint32_t* epoch,
+                             const int32_t* train_labels, int ntrain, const int32_t* qt,
+                             uint64_t mixup_seed, int32_t* out, hipStream_t st);
 void launch_fc1_bwd(const __bf16* dh, const __bf16* dht, int ldt, const __bf16* pool,
                     const __bf16* wf1t, int B, float* gwf1, __bf16* dpool, const float* head_slab,
                     int head_blocks, float* gwf2, float* gbf2, float* gbf1, double* metrics,

@@ -1,7 +1,8 @@
 // Philox4x32-10 (Salmon et al., Random123): the counter-based generator behind every random
 // draw of the device code -- the augmenting gather (augment.hip, counter (index, epoch, 0, 0)),
-// the dropout head (cnn_head_drop.hip, counter (index, epoch, 1, unit >> 3)) and the elastic
-// gather's control points (augment.hip, counter (index, epoch, 2, point)).  The CPU twin
+// the dropout head (cnn_head_drop.hip, counter (index, epoch, 1, unit >> 3)), the elastic
+// gather's control points (augment.hip, counter (index, epoch, 2, point)) and the mixup pairs
+// (kernels/mixup.h, counter (index, epoch, 3, 0)).  The CPU twin
 // is data/augment.py philox4x32_10; tests/test_augment_cpu.py pins it to the Random123 vectors.
 #pragma once
 #include <hip/hip_runtime.h>

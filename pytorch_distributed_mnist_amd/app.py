@@ -25,6 +25,7 @@ from .config import parse_args, usage_error
 from .data import sampler
 from .data.augment import spec_from_args
 from .data.dropout import spec_from_args as dropout_from_args
+from .data.mixup import spec_from_args as mixup_from_args
 from .data.mnist import load_split
 from .engine import Trainer
 from .models.reference import MODULES
@@ -217,6 +218,8 @@ def run(args):
     augment = None if args.evaluate else spec_from_args(args)
     # dropout on the CNN's hidden units (--dropout): likewise
     dropout = None if args.evaluate else dropout_from_args(args)
+    # mixup (--mixup): likewise
+    mixup = None if args.evaluate else mixup_from_args(args)
     # per-step learning-rate schedule (--lr-schedule / --lr-warmup / --lr-min): likewise; None
     # with the defaults, and then the host's per-epoch adjust_learning_rate below is all there is
     schedule = None
@@ -231,7 +234,7 @@ def run(args):
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
                            args.batch_size, use_graphs=args.graphs, augment=augment,
                            dropout=dropout, schedule=schedule, label_smoothing=smoothing,
-                           ema=ema)
+                           ema=ema, mixup=mixup)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises

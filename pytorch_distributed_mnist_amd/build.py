@@ -81,6 +81,7 @@ FILE_FLAGS = {
     "kernels/fc1_bwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "kernels/cnn_head.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
     "kernels/cnn_head_drop.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # its twin
+    "kernels/cnn_head_mix.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],    # and its
 }
 
 

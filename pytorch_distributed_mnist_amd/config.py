@@ -13,7 +13,7 @@ Additions are opt-in and default to the reference's behaviour:
 ``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-elastic`` / ``--aug-seed``,
 dropout on the CNN's hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
 ``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
-``--label-smoothing``, and the exponential moving average of the weights, ``--ema-decay`` /
+``--label-smoothing``, mixup, ``--mixup`` / ``--mixup-seed``, and the exponential moving average of the weights, ``--ema-decay`` /
 ``--ema-warmup``.
 """
 from __future__ import annotations
@@ -189,6 +189,19 @@ def build_parser() -> argparse.ArgumentParser:
                         '0 = off), as torch\'s cross_entropy(label_smoothing=E); the printed train '
                         'loss is the smoothed loss, the test loss stays the plain NLL. Like --lr, '
                         'it is given again on --resume; --evaluate ignores it')
+    # mixup (data/mixup.py; no defaults, as above: absent = 0 = off)
+    g.add_argument('--mixup', metavar='A', type=_ranged(float, 0.0, 10.0),
+                   default=argparse.SUPPRESS,
+                   help='--arch cnn: mixup (Zhang et al. 2018) in training steps: every sample is '
+                        'blended with a partner drawn from the whole training set, image and '
+                        'target alike, with weight lambda ~ Beta(A, A) folded to >= 1/2 (0 < A '
+                        '<= 10, default 0 = off); the printed train loss is the mixed loss, '
+                        'train acc counts the primary sample\'s label; evaluation is never mixed')
+    g.add_argument('--mixup-seed', metavar='N', type=_ranged(int, 0, 2 ** 64 - 1),
+                   default=argparse.SUPPRESS,
+                   help='seed of the mixup draws (default: --seed if given, else 0); a sample\'s '
+                        'partner and weight depend on (seed, epoch, dataset index) only. Like '
+                        '--lr, --mixup is given again on --resume; --evaluate ignores it')
     # exponential moving average of the weights (optim/ema.py; no defaults, as above: absent = off)
     g.add_argument('--ema-decay', metavar='D', type=_ema_decay, default=argparse.SUPPRESS,
                    help='keep an exponential moving average of the weights, e += (1 - D) (p - e) '
@@ -211,6 +224,9 @@ def parse_args(argv=None):
                      "the evaluation pass)")
     if getattr(args, "dropout", 0.0) > 0.0 and args.arch == "linear":
         parser.error("argument --dropout: --arch linear has no hidden layer to drop "
+                     "(use --arch cnn)")
+    if getattr(args, "mixup", 0.0) > 0.0 and args.arch == "linear":
+        parser.error("argument --mixup: only the CNN's training head mixes targets "
                      "(use --arch cnn)")
     if hasattr(args, "lr_min") and getattr(args, "lr_schedule", "step") in ("step", "constant"):
         parser.error("argument --lr-min: --lr-schedule {} has no final rate (use --lr-schedule "

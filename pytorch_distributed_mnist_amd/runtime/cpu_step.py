@@ -26,13 +26,16 @@ def _leaf_params(arena):
 
 def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, metrics_buf,
                    dropout=None, dataset_index=None, epoch=None, lr=None, label_smoothing=0.0,
-                   ema=None):
+                   ema=None, mixup=None):
     """dropout (a data.dropout.DropoutSpec, CNN): the hidden units of the batch's samples
     `dataset_index` are masked by their (seed, epoch, sample, unit) draws.  lr: this step's
     scheduled learning rate (optim/schedule.py), set on the optimizer before its step.
     label_smoothing (E in 0..1): the criterion's targets are (1 - E) onehot + E / 10, and the
     loss added to the metrics is the smoothed one.  ema (an optim.ema.WeightEma): the averaged
-    weights take in the step's updated weights, ema += w (p - ema), after the optimizer."""
+    weights take in the step's updated weights, ema += w (p - ema), after the optimizer.
+    mixup ((partner labels int64 [N], lambda fp32 [N]), data/mixup.py; `images_u8` are the mixed
+    images): the criterion is the per-sample weighted one, mean of lambda loss(y) +
+    (1 - lambda) loss(y2); correct still counts `labels`."""
     x = normalize_reference(images_u8)
     mult = None
     if dropout is not None:
@@ -41,7 +44,13 @@ def train_step_cpu(model: str, arena, images_u8, labels, reducer, optimizer, met
     with torch.enable_grad():
         leaves, views = _leaf_params(arena)
         logits = functional_forward(model, views, x, mult)
-        if label_smoothing > 0.0:
+        if mixup is not None:
+            y2, lam = mixup
+            e = float(label_smoothing)
+            loss = (lam * F.cross_entropy(logits, labels, reduction="none", label_smoothing=e) +
+                    (1.0 - lam) * F.cross_entropy(logits, y2, reduction="none",
+                                                  label_smoothing=e)).mean()
+        elif label_smoothing > 0.0:
             loss = F.cross_entropy(logits, labels, label_smoothing=label_smoothing)
         else:
             loss = F.cross_entropy(logits, labels)

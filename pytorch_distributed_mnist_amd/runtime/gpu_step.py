@@ -102,6 +102,24 @@ class GpuStepBase:
             from ..data.dropout import tag_labels
             self.train_labels = tag_labels(prog.train_split.labels).to(dev).contiguous()
             self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        # mixup (data/mixup.py): the epoch gather blends every image with its partner's and the
+        # head mixes the targets, both from the same (seed, epoch, dataset index) draw.  The head
+        # learns a row's dataset index and the epoch as the dropout head does, so the tagged
+        # training labels and the epoch word are there with mixup on, dropout or not; the
+        # quantile table (and, without augmentation, the identity transform's tables) are
+        # uploaded once, here, never during a capture
+        self.mixup = getattr(prog, "mixup", None)
+        self._mix_table = None
+        if self.mixup is not None:
+            from ..data.dropout import tag_labels
+            if self.dropout is None:
+                self.train_labels = tag_labels(prog.train_split.labels).to(dev).contiguous()
+                self._epoch_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._mix_table = torch.from_numpy(self.mixup.table().copy()).to(dev)
+            if self._aug_tables is None:
+                from ..data.augment import AugmentSpec
+                self._aug_tables = tuple(torch.from_numpy(t).to(dev)
+                                         for t in AugmentSpec().tables())
         # label smoothing of the training heads (--label-smoothing E): a per-run constant, passed
         # to the head launch as a kernel argument and baked into the graphs; 0: off, and the
         # step launches the plain heads
@@ -167,7 +185,22 @@ class GpuStepBase:
         n = self._n_epoch
         buf = self._stage(idx)
         with torch.cuda.stream(stream):
-            if self.augment is None:
+            if self.mixup is not None:
+                # --mixup: always the mixup twin of the elastic gather; without augmentation
+                # its ranges are zero (the identity tables), which is the plain mixed gather
+                a = self.augment
+                cosq, sinq, invz = self._aug_tables
+                self.C.gather_epoch_mixup(self.train_images, self.train_labels, buf[0],
+                                          self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
+                                          self.ep_labels[half * n:(half + 1) * n],
+                                          max_wgs=0, cosq=cosq, sinq=sinq, invz=invz,
+                                          shift=0 if a is None else a.shift, epoch=int(epoch),
+                                          seed=0 if a is None else a.seed,
+                                          elastic_q=0 if a is None else a.elastic_q,
+                                          qt=self._mix_table,
+                                          ntrain=self.train_images.shape[0],
+                                          mixup_seed=self.mixup.seed)
+            elif self.augment is None:
                 self.C.gather_epoch(self.train_images, self.train_labels, buf[0],
                                     self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
                                     self.ep_labels[half * n:(half + 1) * n],
@@ -218,21 +251,23 @@ class GpuStepBase:
         augmentation on, the gathers transform each image by its (seed, epoch, sample) draw,
         so the number is required; with dropout on, the head draws its masks from it (the
         epoch word is filled here, in stream order: behind every step of the previous epoch
-        queued so far, ahead of this epoch's); without either, it is not used.
+        queued so far, ahead of this epoch's); with mixup on, the gather and the head both
+        draw the pairs from it; without any of them, it is not used.
         """
         if self.schedule is not None:
             if epoch is None:
                 raise ValueError("a learning-rate schedule is on: set_train_indices needs the "
                                  "epoch number")
             self._sched_epoch = int(epoch)
-        if self.augment is None and self.dropout is None:
+        if self.augment is None and self.dropout is None and self.mixup is None:
             epoch = None
         elif epoch is None:
-            raise ValueError(("augmentation" if self.augment is not None else "dropout") +
+            raise ValueError(("augmentation" if self.augment is not None else
+                              "dropout" if self.dropout is not None else "mixup") +
                              " is on: set_train_indices needs the epoch number")
         else:
             epoch = int(epoch)
-            if self.dropout is not None and not 0 <= epoch < 2 ** 31:
+            if self._epoch_dev is not None and not 0 <= epoch < 2 ** 31:
                 raise ValueError(f"epoch {epoch} does not fit the device epoch word")
         n = idx_cpu.numel()
         cur = torch.cuda.current_stream(self.device)
@@ -551,9 +586,20 @@ class GpuStepBase:
         """The CNN programs' training head: cnn_head, or with dropout on its masking twin
         (cnn_head_drop.hip), which reads the dataset index from the tagged label word and the
         epoch from the device epoch word; with label smoothing on, cnn_head_smooth, or the
-        masking twin with the smoothing passed on."""
-        d, e = self.dropout, self.label_smoothing
-        if d is not None:
+        masking twin with the smoothing passed on; with mixup on, cnn_head_mixup, which takes
+        dropout and smoothing along."""
+        d, e, m = self.dropout, self.label_smoothing, self.mixup
+        if m is not None:
+            # --mixup: the two-class twin of the masking head (cnn_head_mix.hip) whatever else
+            # is on; it recomputes the gather's pairs and reads the partners' labels
+            drop = dict(seed=d.seed, T=d.T, scale=d.scale) if d is not None else {}
+            self.C.cnn_head_mixup(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
+                                  metrics, c0, c1, xg, dh32, epoch=self._epoch_dev,
+                                  train_labels=self.train_labels,
+                                  ntrain=self.train_labels.numel(), qt=self._mix_table,
+                                  mixup_seed=m.seed, lr_sched=self.lr_sched(),
+                                  label_smoothing=e, **drop)
+        elif d is not None:
             smooth = dict(label_smoothing=e) if e > 0.0 else {}
             self.C.cnn_head_dropout(part, splitk, B, bf1, wf2, bf2, ylab, dh, dht, ldt, slab,
                                     metrics, c0, c1, xg, dh32, self._epoch_dev, d.seed, d.T,

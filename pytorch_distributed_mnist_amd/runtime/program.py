@@ -23,6 +23,7 @@ import torch
 
 from ..data.augment import AugmentSpec, augment_batch
 from ..data.dropout import DropoutSpec
+from ..data.mixup import MixupSpec, mix_batch
 from ..data.mnist import image_rows, label_vector
 from ..data.sampler import batch_bounds
 from ..optim.ema import EmaSpec, WeightEma
@@ -54,8 +55,16 @@ class TrainProgram:
                  augment: Optional[AugmentSpec] = None,
                  dropout: Optional[DropoutSpec] = None,
                  schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
-                 ema: Optional[WeightEma] = None):
+                 ema: Optional[WeightEma] = None, mixup: Optional[MixupSpec] = None):
         self.model = model
+        # mixup (data/mixup.py): training steps only -- every sample is blended with a partner
+        # of the whole training set, on the GPU inside the epoch gather (image) and the head
+        # kernel (target), on the CPU per batch.  None or alpha = 0: off, and nothing changes.
+        self.mixup = mixup if mixup is not None and mixup.enabled else None
+        if self.mixup is not None and model != "cnn":
+            raise ValueError(f"mixup is built into the CNN's training head: the {model} model "
+                             "has no such head")
+        self._mix_table = self.mixup.table() if self.mixup is not None else None
         # exponential moving average of the weights (optim/ema.py): a second flat buffer that
         # takes in every step's whole weights after the step's update -- on the GPU the last
         # launch of the step, inside the graphs, on the CPU after optimizer.step().  Training
@@ -133,6 +142,9 @@ class TrainProgram:
         if self.dropout is not None and epoch is None:
             raise ValueError("dropout is on: set_train_indices needs the epoch number "
                              "(the masks are drawn per (seed, epoch, sample, unit))")
+        if self.mixup is not None and epoch is None:
+            raise ValueError("mixup is on: set_train_indices needs the epoch number "
+                             "(the pairs are drawn per (seed, epoch, sample))")
         if self.schedule is not None:
             if epoch is None:
                 raise ValueError("a learning-rate schedule is on: set_train_indices needs the "
@@ -178,11 +190,12 @@ class TrainProgram:
             g0 = 0 if table is None else self._epoch * self.schedule.spe
             for i, (start, size) in enumerate(self._bounds):
                 idx = self.train_idx_cpu[start:start + size]
-                train_step_cpu(self.model, self.arena, self.train_images_cpu(idx),
+                images, mix = self.train_batch_cpu(idx)
+                train_step_cpu(self.model, self.arena, images,
                                self.train_split.labels[idx], self.reducer, self.optimizer, buf,
                                dropout=self.dropout, dataset_index=idx, epoch=self._epoch,
                                lr=None if table is None else float(table[g0 + i]),
-                               label_smoothing=self.label_smoothing, ema=self.ema)
+                               label_smoothing=self.label_smoothing, ema=self.ema, mixup=mix)
         return self.metrics.read(DeviceMetrics.TRAIN)
 
     def set_schedule(self, schedule: Optional[ScheduleSpec]) -> None:
@@ -193,12 +206,25 @@ class TrainProgram:
             self.gpu.set_schedule(schedule)
 
     def train_images_cpu(self, idx: torch.Tensor) -> torch.Tensor:
-        """The CPU path's training batch of the samples `idx` (uint8 [len(idx), 784]), augmented
-        for the installed epoch when augmentation is on."""
-        images = self.train_split.images[idx]
-        if self.augment is None:
-            return images
-        return augment_batch(images, idx, self._epoch, self.augment, self._aug_tables)
+        """The CPU path's training batch of the samples `idx` (uint8 [len(idx), 784]), mixed and
+        augmented for the installed epoch when mixup / augmentation are on."""
+        return self.train_batch_cpu(idx)[0]
+
+    def train_batch_cpu(self, idx: torch.Tensor):
+        """(images, mix): train_images_cpu's batch and, with mixup on, what the criterion needs
+        of the pairs, (partner labels int64 [n], lambda fp32 [n]); else None.  The images are
+        mixed as uint8 first and transformed second, with the primary sample's parameters."""
+        mix = None
+        if self.mixup is None:
+            images = self.train_split.images[idx]
+        else:
+            images, j, q = mix_batch(self.train_split.images, idx, self._epoch, self.mixup,
+                                     self._mix_table)
+            mix = (self.train_split.labels[torch.from_numpy(j)].to(torch.int64),
+                   torch.from_numpy(q).to(torch.float32) / 256.0)
+        if self.augment is not None:
+            images = augment_batch(images, idx, self._epoch, self.augment, self._aug_tables)
+        return images, mix
 
     # -- fc1 optimizer-state sharding (CNN, world size > 1) ------------------------------------
     def shard_supported(self) -> bool:
@@ -345,7 +371,7 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                         augment: Optional[AugmentSpec] = None,
                         dropout: Optional[DropoutSpec] = None,
                         schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
-                        ema: Optional[EmaSpec] = None):
+                        ema: Optional[EmaSpec] = None, mixup: Optional[MixupSpec] = None):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -369,4 +395,4 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
                         use_graphs=use_graphs, augment=augment, dropout=dropout,
                         schedule=schedule, label_smoothing=label_smoothing,
-                        ema=None if ema is None else WeightEma(ema, arena))
+                        ema=None if ema is None else WeightEma(ema, arena), mixup=mixup)

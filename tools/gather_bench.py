@@ -1,5 +1,6 @@
 """GPU time of the epoch gathers at one rank's epoch (n = 60,000 by default): gather_epoch
-(data.hip), gather_epoch_augment and gather_epoch_elastic (augment.hip), on an otherwise idle GPU.
+(data.hip), gather_epoch_augment, gather_epoch_elastic and gather_epoch_mixup (augment.hip), on
+an otherwise idle GPU.
 
     python tools/gather_bench.py [n]
 
@@ -15,6 +16,7 @@ import torch
 
 sys.path.insert(0, ".")
 from pytorch_distributed_mnist_amd.data.augment import AugmentSpec, augment_batch
+from pytorch_distributed_mnist_amd.data.mixup import MixupSpec, mix_batch
 from pytorch_distributed_mnist_amd.data.mnist import synthetic_split
 from pytorch_distributed_mnist_amd.data.sampler import distributed_indices
 from pytorch_distributed_mnist_amd.ops import _ext
@@ -81,6 +83,21 @@ def main():
         want = augment_batch(train.images[order[:k].long()], order[:k].long(), 1, spec)
         assert torch.equal(out_i[:k].cpu(), want), name
         print(f"gather_epoch_elastic {name:30s} {us:8.1f} us")
+    mix = MixupSpec(0.4, 1)
+    qt = torch.from_numpy(mix.table().copy()).cuda()
+    for name, spec in (("mixup 0.4 alone", AugmentSpec(0, 0.0, 0.0, 1)),
+                       ("mixup 0.4, elastic 2", AugmentSpec(0, 0.0, 0.0, 1, 2.0)),
+                       ("mixup 0.4, s 2, r 10, z 0.1, el. 2", AugmentSpec(2, 10.0, 0.1, 1, 2.0))):
+        cosq, sinq, invz = (torch.from_numpy(t).cuda() for t in spec.tables())
+        fn = lambda: C.gather_epoch_mixup(images, labels, idx, out_i, out_l, None, None, 0, 0,
+                                          cosq, sinq, invz, spec.shift, 1, spec.seed,
+                                          spec.elastic_q, qt, n, mix.seed)
+        us = timeit(fn)
+        k = min(n, 2048)
+        sel = order[:k].long()
+        want = augment_batch(mix_batch(train.images, sel, 1, mix)[0], sel, 1, spec)
+        assert torch.equal(out_i[:k].cpu(), want), name
+        print(f"gather_epoch_mixup   {name:30s} {us:8.1f} us")
 
 
 if __name__ == "__main__":

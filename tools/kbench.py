@@ -2,6 +2,8 @@
 import sys
 import torch
 sys.path.insert(0, ".")
+from pytorch_distributed_mnist_amd.data.dropout import tag_labels
+from pytorch_distributed_mnist_amd.data.mixup import MixupSpec
 from pytorch_distributed_mnist_amd.data.mnist import synthetic_split
 from pytorch_distributed_mnist_amd.data.sampler import distributed_indices
 from pytorch_distributed_mnist_amd.runtime.program import build_local_program
@@ -67,6 +69,8 @@ def main():
       avg = torch.zeros_like(p.arena.params)
       ema = lambda nt: C.ema_update(p.arena.params, avg, p.arena.spec.total, 0.0009765625, False,
                                     0.9990234375, c1, 0, nt=nt)
+      tagged = tag_labels(train.labels).cuda()
+      qt = torch.from_numpy(MixupSpec(0.4).table().copy()).cuda()
       ks = {
           "ema": lambda: ema(False),
           "ema_nt": lambda: ema(True),
@@ -90,6 +94,14 @@ def main():
                                                        st.dh, st.dht, ldt, st.head_slab,
                                                        st.metrics.train_view(), None, None, None,
                                                        None, 0.1),
+          # the masking head's two-class twin (--mixup 0.4, p = 0.5): the row's pair is drawn
+          # from the label word (untagged: sample 0's pair in every row, the same work), the
+          # partner's label read from the tagged training labels
+          "cnn_head_mixup": lambda: C.cnn_head_mixup(st.part, S, B, P["fc1.bias"], P["fc2.weight"],
+                                                     P["fc2.bias"], st.ylab, st.dh, st.dht, ldt,
+                                                     st.head_slab, st.metrics.train_view(), None,
+                                                     None, None, None, epoch_word, 1, 32768, 2.0,
+                                                     tagged, tagged.numel(), qt, 1),
           "cnn_head_step": lambda: head(),
           "cnn_head_sched": lambda: head(lr_sched=sched),
           "fc1_bwd": lambda: C.fc1_bwd(st.dh, st.dht, ldt, st.pool, st.current_wf1t(), B, G["fc1.weight"],
@@ -108,10 +120,13 @@ def main():
       line = []
       for name, fn in ks.items():
           us = timeit(fn)
-          if name not in ("cnn_head_dropout", "cnn_head_smooth", "cnn_head_step",
+          if name not in ("cnn_head_dropout", "cnn_head_smooth", "cnn_head_mixup", "cnn_head_step",
                           "cnn_head_sched", "ema", "ema_nt"):            # variants, opt-in launches
               tot += us
           line.append(f"{name}={us:.1f}")
+      # the mixup head against the head it is the twin of, interleaved
+      pairs = [(timeit(ks["cnn_head_dropout"]), timeit(ks["cnn_head_mixup"])) for _ in range(4)]
+      line.append("dropout|mixup x4: " + " ".join(f"{a:.2f}|{b:.2f}" for a, b in pairs))
       st.ctr.zero_()   # each step advances the data counter (rows are clamped past the epoch)
       step = timeit(lambda: st._train_impl(B), 8)
       print(f"B={B:5d} S={S} ipb={ipb} bands={bands} " + " ".join(line) + f" | sum={tot:.1f}us step={step:.1f}us "

@@ -990,6 +990,35 @@ void lin_predict(at::Tensor images, c10::optional<at::Tensor> labels, at::Tensor
                      o.metrics, cur_stream(images));
 }
 
+// Test-time augmentation (kernels/tta.hip): logp_views fp32 [V, n, 10], the V per-view
+// log-softmax rows of n images, V in 1..32, combined into logp / pred (and, with labels,
+// confusion / metrics) as the prediction heads write them.  lnV is float32(log(float64(V))),
+// formed here.
+void tta_reduce(at::Tensor logp_views, c10::optional<at::Tensor> labels, at::Tensor logp,
+                at::Tensor pred, c10::optional<at::Tensor> confusion,
+                c10::optional<at::Tensor> metrics) {
+  c10::DeviceGuard g(logp_views.device());
+  need(logp_views, at::kFloat, "logp_views");
+  TORCH_CHECK(logp_views.dim() == 3 && logp_views.size(2) == CNN_NCLS,
+              "logp_views must be [V, n, 10]");
+  const int64_t V = logp_views.size(0), n = logp_views.size(1);
+  TORCH_CHECK(V >= 1 && V <= 32, "logp_views holds ", V, " views, expected 1..32");
+  TORCH_CHECK(V * n <= INT32_MAX / (CNN_NCLS * 4), "too many rows for one launch");
+  const bool labelled = labels.has_value() && labels->defined();
+  if (labelled) {
+    need(*labels, at::kInt, "labels");
+    TORCH_CHECK(labels->numel() == n, "labels must be [n]");
+  }
+  const PredictOut o = check_predict_out(n, labelled, logp, pred, confusion, metrics);
+  need_aligned(logp_views.data_ptr(), 8, "logp_views");
+  need_aligned(logp.data_ptr(), 8, "logp");
+  if (n == 0) return;
+  const float lnV = (float)std::log((double)V);
+  launch_tta_reduce(logp_views.data_ptr<float>(), (int)V, (int)n, lnV,
+                    labelled ? labels->data_ptr<int32_t>() : nullptr, o.logp, o.pred, o.confusion,
+                    o.metrics, cur_stream(logp_views));
+}
+
 
 // fc_update (world size 1, optional): (kind, p, g, m, v or None, shadow, lr, step, beta1,
 // beta2, eps, wd, momentum, dampening, nesterov, grad_scale[, shadow_t_next]) -- the
@@ -1379,6 +1408,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("lin_predict", &lin_predict, py::arg("images"), py::arg("labels"), py::arg("W"),
         py::arg("b"), py::arg("logp"), py::arg("pred"), py::arg("confusion") = py::none(),
         py::arg("metrics") = py::none());
+  m.def("tta_reduce", &tta_reduce, py::arg("logp_views"), py::arg("labels"), py::arg("logp"),
+        py::arg("pred"), py::arg("confusion") = py::none(), py::arg("metrics") = py::none());
   m.def("fc1_bwd", &fc1_bwd, py::arg("dh"), py::arg("dht"), py::arg("ldt"), py::arg("pool"),
         py::arg("wf1t"), py::arg("B"), py::arg("gwf1"), py::arg("dpool"), py::arg("head_slab"),
         py::arg("gwf2"), py::arg("gbf2"), py::arg("gbf1"), py::arg("metrics"),

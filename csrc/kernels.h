@@ -380,6 +380,17 @@ void launch_lin_predict(const uint8_t* images, const int32_t* labels, int n_tota
                         const float* b, float* logp, int32_t* pred, int64_t* confusion,
                         double* metrics, hipStream_t st);
 
+// ---------------------------------------------------------------- test-time augmentation (tta.hip)
+// Combines V per-view log-softmax rows per image, logp_views fp32 [V][n][10], into the log of
+// the mean probability: per class m = max_v l, s = sum_v (ascending) expf(l - m), out = (m +
+// logf(s)) - lnV, lnV = float32(log(float64(V))).  Writes logp fp32 [n][10] and pred int32 [n]
+// (first maximum of out); optional: labels, and with them confusion int64 [10][10]
+// (confusion[y][pred] += 1) and metrics fp64 [3] += (sum -out[y], sum [pred == y], n).  Rows >= n
+// write nothing; V = 1 returns the input bits.  logp_views and logp are 8-byte aligned.
+void launch_tta_reduce(const float* logp_views, int V, int n, float lnV, const int32_t* labels,
+                       float* logp, int32_t* pred, int64_t* confusion, double* metrics,
+                       hipStream_t st);
+
 // diagnostic timestamps (all zero unless built with PDM_STAMPS=1); one buffer per kernel file
 // (cnn_common.h PDM_STAMP_READER)
 void read_stamps_fwd(unsigned long long* host);

@@ -216,6 +216,14 @@ def run(args):
     reducer0 = reducer
     # train-time augmentation (--aug-*): training epochs only; --evaluate ignores the flags
     augment = None if args.evaluate else spec_from_args(args)
+    # test-time augmentation (--tta V): every test pass classifies V views per image, drawn with
+    # the --aug-* ranges and --aug-seed -- the one place where --evaluate reads those flags (as
+    # the ranges of the views only: nothing trains there)
+    tta = getattr(args, "tta", 1)
+    tta_augment = spec_from_args(args) if tta > 1 else None
+    if tta > 1 and rank == 0:
+        out("notice: test-time augmentation: every test pass averages {} views per image "
+            "(the image and {} drawn within the --aug-* ranges)".format(tta, tta - 1))
     # dropout on the CNN's hidden units (--dropout): likewise
     dropout = None if args.evaluate else dropout_from_args(args)
     # mixup (--mixup): likewise
@@ -234,7 +242,7 @@ def run(args):
     program = TrainProgram(args.arch, dtype, arena, optimizer, reducer, train_split, test_split,
                            args.batch_size, use_graphs=args.graphs, augment=augment,
                            dropout=dropout, schedule=schedule, label_smoothing=smoothing,
-                           ema=ema, mixup=mixup)
+                           ema=ema, mixup=mixup, tta=tta, tta_augment=tta_augment)
     if device.type == "cuda":
         # every host sync of the epoch loop waits at most --timeout for the device (and the
         # collectives it is queued behind), then aborts the communicator and raises

@@ -13,8 +13,8 @@ Additions are opt-in and default to the reference's behaviour:
 ``--aug-shift`` / ``--aug-rotate`` / ``--aug-zoom`` / ``--aug-elastic`` / ``--aug-seed``,
 dropout on the CNN's hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
 ``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
-``--label-smoothing``, mixup, ``--mixup`` / ``--mixup-seed``, and the exponential moving average of the weights, ``--ema-decay`` /
-``--ema-warmup``.
+``--label-smoothing``, mixup, ``--mixup`` / ``--mixup-seed``, the exponential moving average of the weights, ``--ema-decay`` /
+``--ema-warmup``, and test-time augmentation, ``--tta``.
 """
 from __future__ import annotations
 
@@ -153,7 +153,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help='seed of the augmentation draws (default: --seed if given, else 0); a '
                         "sample's transform depends on (seed, epoch, dataset index) only. Like "
                         '--lr, the --aug-* flags are given again on --resume; --evaluate ignores '
-                        'them')
+                        'them unless --tta asks for views')
     # dropout on the CNN's hidden units (data/dropout.py; no defaults, as above: absent = 0 = off)
     g.add_argument('--dropout', metavar='P', type=_ranged(float, 0.0, 0.9),
                    default=argparse.SUPPRESS,
@@ -212,6 +212,15 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument('--ema-warmup', action='store_true', default=argparse.SUPPRESS,
                    help='with --ema-decay: the k-th update uses min(D, (1 + k) / (10 + k)), so '
                         'the early average follows the weights')
+    # test-time augmentation (no default, as above: absent = 1 = off)
+    g.add_argument('--tta', metavar='V', type=_ranged(int, 1, 32), default=argparse.SUPPRESS,
+                   help='test-time augmentation: every test pass of the run (each epoch\'s test '
+                        'line and so the model_best choice, --evaluate, --predict-out) classifies '
+                        'each image together with V - 1 views of it distorted within the --aug-* '
+                        'ranges and reports the log of the mean probability (1..32, default 1 = '
+                        'off; V > 1 needs an --aug-* range). Training is unchanged. Like --lr, it '
+                        'is given again on --resume and --evaluate, which then reads the --aug-* '
+                        'flags as the ranges of the views')
     parser.set_defaults(local_rank_given=False)
     return parser
 
@@ -231,6 +240,13 @@ def parse_args(argv=None):
     if hasattr(args, "lr_min") and getattr(args, "lr_schedule", "step") in ("step", "constant"):
         parser.error("argument --lr-min: --lr-schedule {} has no final rate (use --lr-schedule "
                      "linear or cosine)".format(getattr(args, "lr_schedule", "step")))
+    if getattr(args, "tta", 1) > 1 and not (getattr(args, "aug_shift", 0) > 0 or
+                                            getattr(args, "aug_rotate", 0.0) > 0.0 or
+                                            getattr(args, "aug_zoom", 0.0) > 0.0 or
+                                            getattr(args, "aug_elastic", 0.0) > 0.0):
+        parser.error("argument --tta: {} views need a range to be drawn from (give --aug-shift, "
+                     "--aug-rotate, --aug-zoom or --aug-elastic): without one every view is the "
+                     "same image".format(args.tta))
     if hasattr(args, "ema_warmup") and not getattr(args, "ema_decay", 0.0):
         parser.error("argument --ema-warmup: there is no average to warm up (give --ema-decay D)")
     return args

@@ -234,6 +234,37 @@ def augment_batch(images_u8, dataset_index, epoch: int, spec: AugmentSpec, table
     return torch.from_numpy(out) if isinstance(images_u8, torch.Tensor) else out
 
 
+# Test-time augmentation (--tta V): view v = 1..V-1 of row r is augment_batch(images, [r],
+# TTA_EPOCH + v, spec) -- bit 31 of the epoch word keeps the draws apart from every training
+# epoch's (set_train_indices takes epochs below 2^31) -- and view 0 is the image itself.
+TTA_EPOCH = 0x80000000
+MAX_TTA = 32
+
+
+def tta_view(images_u8, start: int, size: int, v: int, spec: AugmentSpec, tables=None):
+    """View ``v`` (0..MAX_TTA-1) of the rows ``start .. start + size`` of ``images_u8`` (uint8
+    [N, 784], NumPy or host torch): uint8 [size, 784] of the same kind.  A row's view depends on
+    its position in ``images_u8`` only, not on the chunk it is asked for in."""
+    if not 0 <= int(v) < MAX_TTA:
+        raise ValueError(f"view {v} is outside 0..{MAX_TTA - 1}")
+    rows = images_u8[start:start + size]
+    if v == 0:
+        return rows
+    return augment_batch(rows, np.arange(start, start + rows.shape[0], dtype=np.int64),
+                         TTA_EPOCH + int(v), spec, tables)
+
+
+def check_tta(views, spec) -> int:
+    """The view count of a test-time augmentation as an int in 1..MAX_TTA; more than one view
+    needs an enabled ``spec`` (all views would be the same image otherwise).  ValueError."""
+    if int(views) != views or not 1 <= int(views) <= MAX_TTA:
+        raise ValueError(f"tta must be an integer in 1..{MAX_TTA}, got {views!r}")
+    if int(views) > 1 and (spec is None or not spec.enabled):
+        raise ValueError(f"tta = {views} needs an augmentation range (shift, rotate, zoom or "
+                         "elastic): without one every view is the same image")
+    return int(views)
+
+
 def spec_from_args(args):
     """The AugmentSpec of a parsed command line (None when no --aug-* range was given):
     --aug-seed defaults to --seed when that is given, else 0."""

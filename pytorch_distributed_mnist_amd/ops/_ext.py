@@ -60,3 +60,10 @@ def require():
 
 def available() -> bool:
     return load(required=False) is not None
+
+
+def tta_reduce(logp_views, labels, logp, pred, confusion=None, metrics=None) -> None:
+    """Test-time augmentation's combination on the device (csrc/kernels/tta.hip): logp_views
+    fp32 [V, n, 10] -> logp fp32 [n, 10], pred int32 [n] and, with labels (int32 [n]), the
+    optional confusion int64 [10, 10] and metrics fp64 [3] additions; on the current stream."""
+    require().tta_reduce(logp_views, labels, logp, pred, confusion, metrics)

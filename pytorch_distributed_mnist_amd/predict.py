@@ -14,11 +14,13 @@ the GPU the images go through the evaluation forward and the prediction head ker
 from __future__ import annotations
 
 from types import SimpleNamespace
+from typing import Optional
 
 import numpy as np
 import torch
 
 from .app import resolve_dtype
+from .data.augment import AugmentSpec, check_tta
 from .data.mnist import IMAGE_PIXELS, MnistSplit, NUM_CLASSES
 from .models.specs import get_spec
 from .optim.flat import build_optimizer
@@ -41,16 +43,24 @@ class Predictor:
         """images: uint8 [N, 28, 28] or [N, 784] (raw pixels; normalisation happens inside), as
         a torch tensor or a NumPy array, N >= 1; labels: N class indices, optional.  Returns
         log_probs fp32 [N, 10], pred int64 [N] and confusion int64 [10, 10] (None without
-        labels), on the host."""
+        labels), on the host.  With test-time augmentation on (``load_predictor(tta=V,
+        augment=spec)``) log_probs is the log of the mean probability over the V views."""
         return self.program.predict(images, labels)
 
 
 def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
-                   dtype: str = "auto", ema: bool = False) -> Predictor:
+                   dtype: str = "auto", ema: bool = False, tta: int = 1,
+                   augment: Optional[AugmentSpec] = None) -> Predictor:
     """Build ``arch`` ("linear" or "cnn") on ``device`` ("auto", "cuda" or "cpu") and load the
     checkpoint's weights -- with ``ema=True`` its averaged weights (``ema_state_dict``, written
     by runs with ``--ema-decay``; a checkpoint without them raises KeyError).  A checkpoint of
-    another architecture raises the arena's ``load_state_dict`` error."""
+    another architecture raises the arena's ``load_state_dict`` error.
+
+    ``tta`` (1..32) and ``augment`` (an ``AugmentSpec``): test-time augmentation, as ``--tta V``
+    with the run's ``--aug-*`` flags -- ``predict`` combines ``tta`` views per image, view 0 the
+    image itself and the others drawn with ``augment``'s ranges and seed for the row's position
+    in ``images``.  ``tta > 1`` without an enabled spec raises ValueError."""
+    tta = check_tta(tta, augment)
     dev = pick_device(0, device)
     spec = get_spec(arch)
     arena = FlatArena(spec, dev)
@@ -67,7 +77,7 @@ def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
     empty = MnistSplit(torch.empty(0, IMAGE_PIXELS, dtype=torch.uint8),
                        torch.empty(0, dtype=torch.int64), "none")
     program = TrainProgram(arch, resolve_dtype(dtype, arch, dev), arena, opt, reducer, empty, empty,
-                           batch_size=1, use_graphs=False)
+                           batch_size=1, use_graphs=False, tta=tta, tta_augment=augment)
     if dev.type == "cuda":
         program.sync_fn = lambda what: torch.cuda.synchronize(dev)
     return Predictor(program)

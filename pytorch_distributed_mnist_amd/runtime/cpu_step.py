@@ -106,6 +106,33 @@ def predict_step_cpu(model: str, arena, images_u8, labels=None):
 
 
 @torch.no_grad()
+def tta_reduce_cpu(logp_views, labels=None):
+    """Test-time augmentation's combination (the CPU twin and oracle of csrc/kernels/tta.hip):
+    ``logp_views`` fp32 [V, N, 10], the V per-view log-softmax rows, to the log of the mean
+    probability, per class in fp32 as docs/kernels.md "Test-time augmentation" has it --
+    m = max_v l, s = sum over v ascending of exp(l - m), out = (m + log(s)) - lnV with lnV =
+    float32(log(float64(V))).  Returns predict_step_cpu's triple: (out fp32 [N, 10], pred int64
+    [N], the first maximum of out, confusion int64 [10, 10] or None without labels)."""
+    import math
+    lv = torch.as_tensor(logp_views)
+    if lv.dim() != 3 or lv.dtype != torch.float32 or lv.shape[0] < 1:
+        raise ValueError(f"logp_views must be fp32 [V >= 1, N, C], got {lv.dtype} {tuple(lv.shape)}")
+    m = lv.amax(dim=0)
+    s = torch.zeros_like(m)
+    for v in range(lv.shape[0]):
+        s = s + torch.exp(lv[v] - m)
+    lnv = torch.tensor(math.log(float(lv.shape[0])), dtype=torch.float64).to(torch.float32)
+    out = (m + torch.log(s)) - lnv
+    pred = out.argmax(dim=1)
+    confusion = None
+    if labels is not None:
+        ncls = out.shape[1]
+        confusion = torch.bincount(labels.to(torch.int64) * ncls + pred,
+                                   minlength=ncls * ncls).view(ncls, ncls)
+    return out, pred, confusion
+
+
+@torch.no_grad()
 def eval_step_cpu(model: str, arena, images_u8, labels, metrics_buf):
     x = normalize_reference(images_u8)
     views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}

@@ -138,6 +138,8 @@ class GpuStepBase:
         # baked into the graphs, which are re-captured when it changes (_ema_sync)
         self.ema = getattr(prog, "ema", None)
         self._ema_off = None
+        # test-time augmentation (predict_tta): the views' Q14 tables on the device, per spec
+        self._tta_table_cache = {}
         self._epoch_start = 0
         self._gather_stream = None       # stream of the ahead-of-time gathers
         self._ring = None                # pinned staging buffers of the epoch orders
@@ -695,6 +697,88 @@ class GpuStepBase:
         """(log_probs, pred, confusion | None) of any N >= 1 images, on the device; enqueued on
         the current stream (the caller synchronises before reading)."""
         raise NotImplementedError
+
+    # -- test-time augmentation ----------------------------------------------------
+    # rows per view gather and reduce launch: the whole 10,000-image test split in one (the
+    # gathers take a workgroup per 64 rows, so 2048 rows would occupy 32 of the CUs; the CNN
+    # programs' predict() walks its own 2048-row chunks inside); 13 MB of view rows at V = 32
+    TTA_CHUNK = 16384
+
+    def _tta_tables(self, spec):
+        """The Q14 tables of `spec` on the device, uploaded once per spec (never in a capture)."""
+        t = self._tta_table_cache.get(spec)
+        if t is None:
+            t = tuple(torch.from_numpy(a).to(self.device) for a in spec.tables())
+            self._tta_table_cache[spec] = t
+        return t
+
+    def tta_view(self, images: torch.Tensor, start: int, b: int, v: int, spec, out=None,
+                 scratch=None) -> torch.Tensor:
+        """View `v` of the rows start .. start + b of the device images (uint8 [N, 784]): uint8
+        [b, 784] on the device, data/augment.py's tta_view bit for bit.  View 0 is the rows
+        themselves; the others come from the augmenting epoch gathers, asked for the rows
+        `start + arange(b)` in epoch TTA_EPOCH + v, so a row's draw is that of its position in
+        `images`.  out (uint8 [>= b * 784]) and scratch ((labels int32 [N], out_labels int32
+        [>= b]): the gathers copy a label per row) are allocated here unless given."""
+        from ..data.augment import MAX_TTA, TTA_EPOCH
+        if not 0 <= v < MAX_TTA:
+            raise ValueError(f"view {v} is outside 0..{MAX_TTA - 1}")
+        n = images.shape[0]
+        if not (0 <= start and b >= 1 and start + b <= n):
+            raise ValueError(f"rows {start}..{start + b} are not rows of {n} images")
+        if v == 0:
+            return images[start:start + b]
+        dev = self.device
+        if out is None:
+            out = torch.empty(b * 784, dtype=torch.uint8, device=dev)
+        if scratch is None:
+            scratch = (torch.zeros(n, dtype=torch.int32, device=dev),
+                       torch.empty(b, dtype=torch.int32, device=dev))
+        idx = torch.arange(start, start + b, dtype=torch.int32, device=dev)
+        cosq, sinq, invz = self._tta_tables(spec)
+        kw = dict(max_wgs=0, cosq=cosq, sinq=sinq, invz=invz, shift=spec.shift,
+                  epoch=TTA_EPOCH + v, seed=spec.seed)
+        if spec.elastic > 0.0:
+            self.C.gather_epoch_elastic(images, scratch[0], idx, out, scratch[1],
+                                        elastic_q=spec.elastic_q, **kw)
+        else:
+            self.C.gather_epoch_augment(images, scratch[0], idx, out, scratch[1], **kw)
+        return out[:b * 784].view(b, 784)
+
+    def predict_tta(self, images_u8: torch.Tensor, labels, ws, spec, views: int, chunk=None,
+                    metrics=None):
+        """predict() with test-time augmentation: (log_probs, pred, confusion | None) of any
+        N >= 1 images, combined over `views` views per image (data/augment.py check_tta: 1..32,
+        and an enabled `spec` for more than one).  Per chunk of `chunk` rows (default
+        TTA_CHUNK) every view goes through this step's own predict() with the weight set `ws`
+        (None: the training weights) and one tta_reduce launch (csrc/kernels/tta.hip) writes
+        the chunk's slices of the outputs; with `metrics` (fp64 [3], needs labels) it also adds
+        the evaluation sums (sum of -log_probs[y], correct, rows).  Allocates, so not inside a
+        graph capture; nothing of the training step is touched."""
+        from ..data.augment import check_tta
+        views = check_tta(views, spec)
+        chunk = self.TTA_CHUNK if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
+        if metrics is not None and lab is None:
+            raise ValueError("metrics need labels")
+        n = images.shape[0]
+        dev = self.device
+        chunk = min(chunk, n)
+        stack = torch.empty(views * chunk * 10, dtype=torch.float32, device=dev)
+        out = torch.empty(chunk * 784, dtype=torch.uint8, device=dev)
+        scratch = (torch.zeros(n, dtype=torch.int32, device=dev),
+                   torch.empty(chunk, dtype=torch.int32, device=dev))
+        for s in range(0, n, chunk):
+            b = min(chunk, n - s)
+            st = stack[:views * b * 10].view(views, b, 10)
+            for v in range(views):
+                x = self.tta_view(images, s, b, v, spec, out, scratch)
+                st[v].copy_(self.predict(x, None, ws)[0])
+            self.C.tta_reduce(st, None if lab is None else lab[s:s + b], logp[s:s + b],
+                              pred[s:s + b], conf, metrics)
+        return logp, pred, conf
 
 
 class LinearStep(GpuStepBase):

@@ -21,7 +21,7 @@ from typing import Optional
 
 import torch
 
-from ..data.augment import AugmentSpec, augment_batch
+from ..data.augment import AugmentSpec, augment_batch, check_tta, tta_view
 from ..data.dropout import DropoutSpec
 from ..data.mixup import MixupSpec, mix_batch
 from ..data.mnist import image_rows, label_vector
@@ -29,7 +29,7 @@ from ..data.sampler import batch_bounds
 from ..optim.ema import EmaSpec, WeightEma
 from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
-from .cpu_step import eval_step_cpu, predict_step_cpu, train_step_cpu
+from .cpu_step import eval_step_cpu, predict_step_cpu, train_step_cpu, tta_reduce_cpu
 from .structure import StepStructure
 
 
@@ -55,8 +55,15 @@ class TrainProgram:
                  augment: Optional[AugmentSpec] = None,
                  dropout: Optional[DropoutSpec] = None,
                  schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
-                 ema: Optional[WeightEma] = None, mixup: Optional[MixupSpec] = None):
+                 ema: Optional[WeightEma] = None, mixup: Optional[MixupSpec] = None,
+                 tta: int = 1, tta_augment: Optional[AugmentSpec] = None):
         self.model = model
+        # test-time augmentation (--tta V): evaluate() and predict() classify every image
+        # together with V - 1 distorted views of it and combine the V log-softmax rows into the
+        # log of the mean probability (docs/kernels.md "Test-time augmentation").  The views'
+        # ranges are `tta_augment` (None: `augment`, the training ranges).  1: off, and both
+        # run exactly what they run without it.  Training never sees any of this.
+        self.set_tta(tta, tta_augment if tta_augment is not None else augment)
         # mixup (data/mixup.py): training steps only -- every sample is blended with a partner
         # of the whole training set, on the GPU inside the epoch gather (image) and the head
         # kernel (target), on the CPU per batch.  None or alpha = 0: off, and nothing changes.
@@ -198,6 +205,14 @@ class TrainProgram:
                                label_smoothing=self.label_smoothing, ema=self.ema, mixup=mix)
         return self.metrics.read(DeviceMetrics.TRAIN)
 
+    def set_tta(self, views: int, spec: Optional[AugmentSpec]) -> None:
+        """Install the test-time augmentation: `views` views per image (1..32; 1 = off) drawn
+        with the ranges and the seed of `spec`, which more than one view needs enabled."""
+        spec = spec if spec is not None and spec.enabled else None
+        self.tta = check_tta(views, spec)
+        self.tta_augment = spec
+        self._tta_tables = spec.tables() if spec is not None else None
+
     def set_schedule(self, schedule: Optional[ScheduleSpec]) -> None:
         """Install (or with None remove) the learning-rate schedule; on the GPU the graphs are
         re-captured on next use."""
@@ -321,7 +336,25 @@ class TrainProgram:
         self.metrics.reset(DeviceMetrics.EVAL)
         n = len(self.test_split)
         arena = self._eval_arena(average)
-        if self.gpu is not None:
+        if self.tta > 1:
+            # test-time augmentation: the combined rows' sums, sum of -log_probs[y], correct
+            # and rows, in fp64 -- on the GPU added by tta_reduce, chunk by chunk
+            if self.gpu is not None:
+                self.gpu.predict_tta(self.gpu.test_images, self.gpu.test_labels,
+                                     None if arena is self.arena else self.gpu.weight_set(arena),
+                                     self.tta_augment, self.tta,
+                                     metrics=self.metrics.eval_view())
+                if self.sync_fn is not None:
+                    self.sync_fn("evaluation")
+            else:
+                y = self.test_split.labels.to(torch.int64)
+                logp, pred, _ = self._predict_tta_cpu(arena, self.test_split.images, None,
+                                                      self.tta)
+                buf = self.metrics.buf[3:6]
+                buf[0] += -logp.gather(1, y[:, None]).to(torch.float64).sum()
+                buf[1] += int(pred.eq(y).sum())
+                buf[2] += n
+        elif self.gpu is not None:
             self.gpu.evaluate(None if arena is self.arena else self.gpu.weight_set(arena))
             if self.sync_fn is not None:
                 self.sync_fn("evaluation")
@@ -333,12 +366,16 @@ class TrainProgram:
         return self.metrics.read(DeviceMetrics.EVAL)
 
     @torch.no_grad()
-    def predict(self, images=None, labels=None, average: Optional[bool] = None) -> Prediction:
+    def predict(self, images=None, labels=None, average: Optional[bool] = None,
+                tta: Optional[int] = None) -> Prediction:
         """Per-sample predictions of the current weights: for ``images`` (uint8 [N, 28, 28] or
         [N, 784], torch or NumPy, any N >= 1; ``labels`` optional), or with no arguments for the
         test split and its labels.  Runs evaluate()'s forward; the metric accumulators are not
-        touched.  ``average``: as evaluate()'s."""
+        touched.  ``average``: as evaluate()'s.  ``tta``: the number of test-time views per
+        image (None: the program's; 1: none); with more than one, log_probs is the log of the
+        views' mean probability, and view v of row r is drawn for r's position in ``images``."""
         arena = self._eval_arena(average)
+        views = self.tta if tta is None else check_tta(tta, self.tta_augment)
         if images is None:
             if labels is not None:
                 raise ValueError("labels without images")
@@ -351,17 +388,37 @@ class TrainProgram:
             if labels is not None:
                 labels = label_vector(labels, images.shape[0])
         if self.gpu is not None:
-            logp, pred, conf = self.gpu.predict(
-                images, labels, None if arena is self.arena else self.gpu.weight_set(arena))
+            ws = None if arena is self.arena else self.gpu.weight_set(arena)
+            if views > 1:
+                logp, pred, conf = self.gpu.predict_tta(images, labels, ws, self.tta_augment,
+                                                        views)
+            else:
+                logp, pred, conf = self.gpu.predict(images, labels, ws)
             if self.sync_fn is not None:
                 self.sync_fn("prediction")
             return Prediction(logp.cpu(), pred.cpu().to(torch.int64),
                               None if conf is None else conf.cpu())
+        if views > 1:
+            return Prediction(*self._predict_tta_cpu(arena, images, labels, views))
         outs = [predict_step_cpu(self.model, arena, images[start:start + size],
                                  None if labels is None else labels[start:start + size])
                 for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)]
         return Prediction(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
                           None if labels is None else sum(o[2] for o in outs))
+
+    def _predict_tta_cpu(self, arena, images, labels, views: int):
+        """The CPU path's predict() with `views` > 1 test-time views: per batch of rows, every
+        view (data/augment.py tta_view) through predict_step_cpu, combined by tta_reduce_cpu."""
+        spec, tables = self.tta_augment, self._tta_tables
+        outs = []
+        for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU):
+            lv = torch.stack([predict_step_cpu(self.model, arena,
+                                               tta_view(images, start, size, v, spec, tables))[0]
+                              for v in range(views)])
+            outs.append(tta_reduce_cpu(lv, None if labels is None else
+                                       labels[start:start + size]))
+        return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
+                None if labels is None else sum(o[2] for o in outs))
 
 
 def build_local_program(arch: str, dtype: str, device, batch_size: int, train_split, test_split,
@@ -371,7 +428,8 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
                         augment: Optional[AugmentSpec] = None,
                         dropout: Optional[DropoutSpec] = None,
                         schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
-                        ema: Optional[EmaSpec] = None, mixup: Optional[MixupSpec] = None):
+                        ema: Optional[EmaSpec] = None, mixup: Optional[MixupSpec] = None,
+                        tta: int = 1, tta_augment: Optional[AugmentSpec] = None):
     """Single-rank program without a process group (tests, bench at N=1, smoke)."""
     from types import SimpleNamespace
 
@@ -395,4 +453,5 @@ def build_local_program(arch: str, dtype: str, device, batch_size: int, train_sp
     return TrainProgram(arch, dtype, arena, opt, reducer, train_split, test_split, batch_size,
                         use_graphs=use_graphs, augment=augment, dropout=dropout,
                         schedule=schedule, label_smoothing=label_smoothing,
-                        ema=None if ema is None else WeightEma(ema, arena), mixup=mixup)
+                        ema=None if ema is None else WeightEma(ema, arena), mixup=mixup,
+                        tta=tta, tta_augment=tta_augment)

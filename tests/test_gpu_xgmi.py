@@ -1,7 +1,7 @@
 """Direct xGMI all-reduce transport (csrc/xgmi.h, csrc/kernels/xgmi.hip).
 
 Single-rank cases run in-process; multi-rank cases run tests/xgmi_worker.py with
-2 and 4 ranks sharing the one GPU of the box (hipIpc across processes, gloo
+2, 3, 4, 6 and 8 ranks sharing the one GPU of the box (hipIpc across processes, gloo
 control plane), which exercises the same peer mappings, flags and push
 schedules as ranks on different GPUs.
 """
@@ -75,29 +75,81 @@ def test_cnn_step_through_xgmi_matches_local(gpu):
     assert torch.equal(out[0], out[1])
 
 
+def _diagnosis(r, logs):
+    """What a failed launch left: the first traceback of the ranks (the launcher's own summary
+    fills the end of its output), the end of the output, and every rank's progress log."""
+    err = r.stderr
+    i = err.find("Traceback")
+    out = [r.stdout[-1500:], err[i:i + 3000] if i >= 0 else "", err[-1500:]]
+    if os.path.isdir(logs):
+        for name in sorted(os.listdir(logs)):
+            with open(os.path.join(logs, name)) as f:
+                out.append(f"--- {name}\n" + f.read()[-800:])
+    return "\n".join(out)
+
+
 def _run_workers(nproc, tmp_path, **extra):
     # a peer that never arrives turns into an error after 10 s instead of a 60 s stall
     # 8-step graphs: the workers' 9-step epochs replay two graphs (the carry crosses a replay
     # boundary) in the step count the cross-transport tolerance below was set for
+    logs = str(tmp_path / "logs")
     env = dict(os.environ, PDM_SHARE_DEVICE="1", PDM_XGMI_OUT=str(tmp_path),
-               PDM_XGMI_TIMEOUT=os.environ.get("PDM_XGMI_TIMEOUT", "10"), PDM_GRAPH_STEPS="8")
+               PDM_XGMI_TIMEOUT=os.environ.get("PDM_XGMI_TIMEOUT", "10"), PDM_GRAPH_STEPS="8",
+               PDM_XGMI_LOG_DIR=os.environ.get("PDM_XGMI_LOG_DIR", logs))
     env.update(extra)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
                         "--master-port", str(free_port()),
                         os.path.join(REPO, "tests", "xgmi_worker.py")],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=150)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.returncode == 0, _diagnosis(r, env["PDM_XGMI_LOG_DIR"])
     return [json.load(open(tmp_path / f"rank{i}.json")) for i in range(nproc)]
 
 
-@pytest.mark.parametrize("nproc", [2, 4])
+# conv2.weight rows kept per world size (xgmi_worker.exchange_unit): all 64 up to 4 ranks
+XCHG_ROWS = {2: 64, 3: 64, 4: 64, 6: 16, 8: 16}
+
+
+@pytest.mark.parametrize("nproc", [2, 3, 4, 6, 8])
 def test_xgmi_optimizer_in_launch_exchange(gpu, tmp_path, nproc):
     """The conv bucket's in-launch exchange inside the optimizer (CnnStep with the streamed
     xgmi transport): N ranks sharing one GPU, slab segments only, against the exact rank-order
-    sum, eager and graph-replayed."""
-    for d in _run_workers(nproc, tmp_path, PDM_XGMI_UNIT="xchg"):
+    sum, eager and graph-replayed; then one slab of randn rows, whose rank-order sum no other
+    order of the ranks reproduces (the reversed order differs on 32 / 44 / 55 / 62 % of the
+    compared columns at 3 / 4 / 6 / 8 ranks; asserted >= 20 % from the reference alone).
+    3, 6 and 8 ranks run without the child-process pre-flight, which the 2-rank test keeps
+    covered: N workers and this process have the GPU open (9 at 8 ranks).
+
+    Every slab workgroup spins until all N ranks' workgroups of its slot have signalled, so on
+    ONE shared GPU all N grids must be resident at once.  optim_kernel takes 74 registers per
+    lane and 16392 B of LDS (the code object's metadata, as tools/kernel_resources.py reads
+    it; no test pins these two figures): 6 workgroups of 256 per CU, 1536 on 256 CUs.  The
+    whole conv geometry, 295 workgroups per rank, fits at 4 ranks (1180) and not at 8 (2360):
+    there the waits end at the device deadline on every rank (error word 0x11, first cause
+    XG_ERR_PEER0).  At 6 and 8 ranks conv2.weight is therefore cut to its first 16 rows
+    (PDM_XGMI_XCHG_ROWS): 72 + 1 + 5 + 1 = 79 workgroups per rank, 474 / 632 in all, which
+    stay resident.  That runs xg_exchange's push rotation over 5 and 7 peers, the rank-order
+    sum over 6 and 8 stage rows, the flag slots of sources 4..7 and the poll with up to 7
+    active lanes; 6.8 s and 6.1 s a launch, beside 8.2 s at 4 ranks (14.3 s at 8 ranks inside
+    the whole suite's run).  Not pinned past 4 ranks:
+    flag slots 79..294 (the same index arithmetic, `src * XG_XSLOTS + slot`, whose slots
+    0..78 run at every src here and 0..294 at src < 4).  Ranks on GPUs of their own share
+    neither CUs nor queues and run the whole geometry.
+
+    A failed launch reports the ranks' first traceback and every rank's progress log
+    (_diagnosis), and the worker writes its error and first-error words into the JSON before
+    check() raises on them."""
+    extra = {} if nproc in (2, 4) else {"PDM_XGMI_PROBE": "0"}
+    extra["PDM_XGMI_XCHG_ROWS"] = str(XCHG_ROWS[nproc])
+    blocks = (XCHG_ROWS[nproc] * 288) // 64 + 1 + 5 + 1
+    for d in _run_workers(nproc, tmp_path, PDM_XGMI_UNIT="xchg", **extra):
+        print(f"rank {d['rank']}: error {d['xchg_error']:#x} first {d['xchg_first_error']:#x} "
+              f"order share {d['xchg_order_share']:.3f} blocks {d['xchg_blocks']} {d['xchg_info']}")
         assert d["xchg_ok"], d
+        assert d["xchg_error"] == 0 and d["xchg_first_error"] == 0, d
+        assert d["xchg_blocks"] == blocks, d
+        if nproc >= 3:       # the randn row makes the order visible (32 % at 3 ranks, from the CPU)
+            assert d["xchg_order_share"] >= 0.20, d
 
 
 def test_xgmi_two_ranks_one_gpu(gpu, tmp_path):

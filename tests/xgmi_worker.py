@@ -107,18 +107,22 @@ def exchange_unit(comm, dev, rank, ws):
     mom = torch.zeros(n, device=dev)
     lr = torch.zeros(1, dtype=torch.float64, device=dev)
     step = torch.ones(1, dtype=torch.int64, device=dev)
-    # (arena offset, rows, cols, slab column) of conv2.weight / .bias, conv1.weight / .bias
-    parts = [(FC, 64, 288, 0), (FC + 18432, 1, 64, C.CNN_CONV_SLAB_DB2),
+    # (arena offset, rows, cols, slab column) of conv2.weight / .bias, conv1.weight / .bias;
+    # PDM_XGMI_XCHG_ROWS keeps conv2.weight's first R rows only (R = 16: 79 slab workgroups
+    # per rank in place of 295, for world sizes whose whole grids one shared GPU cannot hold)
+    rows2 = int(os.environ.get("PDM_XGMI_XCHG_ROWS", "64"))
+    assert 1 <= rows2 <= 64, rows2
+    parts = [(FC, rows2, 288, 0), (FC + 18432, 1, 64, C.CNN_CONV_SLAB_DB2),
              (FC + 18496, 1, 288, C.CNN_CONV_SLAB_DW1), (FC + 18816, 1, 32, C.CNN_CONV_SLAB_DB1)]
     segs = [(off, r, c, None, None, (slab, nslab, col0, SL)) for off, r, c, col0 in parts]
 
-    def launch():
+    def launch(segs=segs):
         C.optim_step(C.OPT_SGD, params, red.out_grads, mom, None, lr, step, 0.0, 0.0, 0.0, 0.0,
                      0.0, 0.0, False, 1.0, segs, xg=red.sync, signal_ch=-1,
                      waits=red.waits_for(segs, exchanged=(1,)), timeout_s=red.timeout_s,
                      xchg=red._native, xchg_bucket=1)
 
-    def expected(scale):
+    def expected(scale, base=base):
         mine = (base * scale).sum(0)                   # this rank's slab sums, per column
         tot = rank_order_sum(mine, ws)
         want = torch.full((CONV,), float("nan"))     # nan: padding, not compared
@@ -129,8 +133,8 @@ def exchange_unit(comm, dev, rank, ws):
     ok = True
     info = []
 
-    def check(tag, scale):
-        got, want = red.out_grads[FC:n].cpu(), expected(scale)
+    def check(tag, scale, base=base):
+        got, want = red.out_grads[FC:n].cpu(), expected(scale, base)
         seg = ~torch.isnan(want)
         good = torch.equal(got[seg], want[seg])
         if not good:
@@ -159,9 +163,43 @@ def exchange_unit(comm, dev, rank, ws):
         torch.cuda.synchronize()
         ok = check(f"graph {it}", 8.0) and ok
         log(f"xchg graph {it} ok={ok}")
-    red.check()
+    # one slab of randn rows: a rank's column sums are the row itself, exact, so only the
+    # cross-rank order is in play -- the result is the rank-order sum of the rows, bit for
+    # bit, which another order of the ranks misses on the share of columns measured below
+    # (both stage parities)
+    row = torch.randn(1, SL, generator=torch.Generator().manual_seed(500 + rank))
+    # from the reference alone: the share of compared columns on which the reversed order
+    # (N-1..0) gives other fp32 bits than the rank order (the test asserts it at N >= 3)
+    rows = [torch.zeros(SL) for _ in range(ws)]
+    dist.all_gather(rows, row.reshape(-1).contiguous())
+    fwd, rev = rows[0].clone(), rows[-1].clone()
+    for q in range(1, ws):
+        fwd += rows[q]
+        rev += rows[ws - 1 - q]
+    used = torch.zeros(SL, dtype=torch.bool)
+    for off, r, c, col0 in parts:
+        used[col0:col0 + r * c] = True
+    order_share = float((fwd.view(torch.int32) != rev.view(torch.int32))[used].float().mean())
+    log(f"xchg order share {order_share:.3f} over {int(used.sum())} columns")
+    slab1 = row.reshape(-1).to(dev).contiguous()
+    segs1 = [(off, r, c, None, None, (slab1, 1, col0, SL)) for off, r, c, col0 in parts]
+    for it in range(2):
+        slab1.copy_((row * (it + 1)).reshape(-1).to(dev))
+        launch(segs1)
+        torch.cuda.synchronize()
+        ok = check(f"randn row {it}", it + 1, row) and ok
+        log(f"xchg randn row {it} ok={ok}")
+    # the error words go into the JSON before check() raises on them
+    err, first = int(red._xgmi.native.error()), int(red._xgmi.native.first_error())
+    log(f"xchg error word {err:#x}, first cause {first:#x}")
+    try:
+        red.check()
+    except RuntimeError as e:
+        ok = False
+        info.append(f"check(): {e}")
     red.close()
-    return {"xchg_ok": bool(ok), "xchg_info": info}
+    return {"xchg_ok": bool(ok), "xchg_info": info, "xchg_error": err, "xchg_first_error": first,
+            "xchg_order_share": order_share, "xchg_blocks": sum((r * c + 63) // 64 for _, r, c, _ in parts)}
 
 
 def train_model(arch, comm, dev, rank, ws, transport):

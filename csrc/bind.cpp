@@ -1283,6 +1283,73 @@ void f32_conv_bwd(at::Tensor a1g, at::Tensor xng, at::Tensor dpool, at::Tensor p
                       slab.data_ptr<float>(), x3, x3 ? w2x_ptr(w2x) : nullptr, cur_stream(a1g));
 }
 
+// ------------------------------------------------------------------ MLP (mlp.hip)
+// the step's rows of both MLP launches: an epoch buffer behind the data-step counter, or rows
+// 0 .. B - 1 of `images`
+static void check_mlp_rows(const at::Tensor& images, const c10::optional<at::Tensor>& ctr,
+                           int64_t bfull, int64_t B) {
+  need(images, at::kByte, "images");
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == MLP_IN && images.size(0) >= 1, "images [N, 784]");
+  need_aligned(images.data_ptr(), 8, "images");
+  TORCH_CHECK(B >= 1 && (!ctr.has_value() ? images.size(0) >= B : B <= bfull), "batch size");
+  if (ctr.has_value()) {
+    need(*ctr, at::kLong, "ctr");
+    TORCH_CHECK(ctr->numel() >= 1, "ctr must hold the data-step counter");
+  }
+}
+
+void mlp_fwd(at::Tensor images, at::Tensor labels, c10::optional<at::Tensor> ctr, int64_t bfull,
+             int64_t B, at::Tensor whi, at::Tensor wlo, at::Tensor part, at::Tensor ylab,
+             int64_t splitk, int64_t spe) {
+  c10::DeviceGuard g(images.device());
+  check_mlp_rows(images, ctr, bfull, B);
+  need(labels, at::kInt, "labels");
+  TORCH_CHECK(labels.numel() == images.size(0), "labels [N]");
+  TORCH_CHECK(splitk == 1 || splitk == 5 || splitk == 25, "splitk must be 1, 5 or 25, got ", splitk);
+  need(whi, at::kBFloat16, "whi");
+  need(wlo, at::kBFloat16, "wlo");
+  TORCH_CHECK(whi.numel() == (int64_t)CNN_HID * MLP_IN && wlo.numel() == whi.numel(),
+              "fc1 weight planes [128, 784]");
+  for (const void* q : {whi.data_ptr(), wlo.data_ptr()}) need_aligned(q, 16, "fc1 weight plane");
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need_min(ylab, at::kInt, B, "ylab");
+  launch_mlp_fwd(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), images.size(0),
+                 ctr.has_value() ? ctr->data_ptr<int64_t>() : nullptr,
+                 step_rows(bfull, ctr.has_value() ? spe : 0, images.size(0)), (int)B,
+                 ptr<__bf16>(whi), ptr<__bf16>(wlo), part.data_ptr<float>(),
+                 ylab.data_ptr<int32_t>(), (int)splitk, cur_stream(images));
+}
+
+void mlp_bwd(at::Tensor images, c10::optional<at::Tensor> ctr, int64_t bfull, int64_t B,
+             at::Tensor dh, int64_t ldt, at::Tensor gw1, at::Tensor head_slab, at::Tensor gwf2,
+             at::Tensor gbf2, at::Tensor gbf1, at::Tensor metrics, int64_t spe,
+             bool ctr_advanced, int64_t head_blocks) {
+  c10::DeviceGuard g(images.device());
+  check_mlp_rows(images, ctr, bfull, B);
+  TORCH_CHECK(ldt % 32 == 0 && ldt >= B, "ldt must be a multiple of 32 and >= B");
+  need_min(dh, at::kFloat, ldt * CNN_HID, "dh32");
+  need(gw1, at::kFloat, "gw1");
+  TORCH_CHECK(gw1.numel() == (int64_t)CNN_HID * MLP_IN, "fc1 grad [128, 784]");
+  need_aligned(gw1.data_ptr(), 16, "gw1");
+  // the head's slab count for ldt rows, unless the caller names a smaller one
+  const int hbmax = cnn_head_blocks((int)(ldt / CNN_HEAD_ROWS));
+  const int hb = head_blocks < 0 ? hbmax : (int)head_blocks;
+  TORCH_CHECK(hb >= 1 && hb <= hbmax, "head_blocks must be in 1..", hbmax);
+  need_min(head_slab, at::kFloat, (int64_t)hb * CNN_HEAD_SLAB, "head slab");
+  need(gwf2, at::kFloat, "gwf2");
+  need(gbf2, at::kFloat, "gbf2");
+  need(gbf1, at::kFloat, "gbf1");
+  TORCH_CHECK(gwf2.numel() == 1280 && gbf2.numel() == 10 && gbf1.numel() == 128, "head grads");
+  need(metrics, at::kDouble, "metrics");
+  need_numel(metrics, 3, "metrics");
+  launch_mlp_bwd(images.data_ptr<uint8_t>(), images.size(0),
+                 ctr.has_value() ? ctr->data_ptr<int64_t>() : nullptr, ctr_advanced ? 1 : 0,
+                 step_rows(bfull, ctr.has_value() ? spe : 0, images.size(0)), (int)B,
+                 dh.data_ptr<float>(), gw1.data_ptr<float>(), head_slab.data_ptr<float>(), hb,
+                 gwf2.data_ptr<float>(), gbf2.data_ptr<float>(), gbf1.data_ptr<float>(),
+                 metrics.data_ptr<double>(), cur_stream(images));
+}
+
 // Upload an instantiated hipGraph (torch.cuda.CUDAGraph.raw_cuda_graph_exec()) to the device
 // on the current stream, so its first replay inside a timed region costs the same as later ones.
 void graph_upload(int64_t exec, int64_t device) {
@@ -1435,6 +1502,13 @@ PYBIND11_MODULE(_C, m) {
     return (int64_t)f32_conv_bwd_blocks((int)B, (int)ipb, x3); }, py::arg("B"), py::arg("ipb") = 1,
     py::arg("x3") = false);
   m.def("cnn_bwd_nblk", &cnn_bwd_nblk, py::arg("B"), py::arg("ipb"), py::arg("bands") = 1);
+  m.def("mlp_fwd", &mlp_fwd, py::arg("images"), py::arg("labels"), py::arg("ctr"), py::arg("bfull"),
+        py::arg("B"), py::arg("whi"), py::arg("wlo"), py::arg("part"), py::arg("ylab"),
+        py::arg("splitk"), py::arg("spe") = 0);
+  m.def("mlp_bwd", &mlp_bwd, py::arg("images"), py::arg("ctr"), py::arg("bfull"), py::arg("B"),
+        py::arg("dh"), py::arg("ldt"), py::arg("gw1"), py::arg("head_slab"), py::arg("gwf2"),
+        py::arg("gbf2"), py::arg("gbf1"), py::arg("metrics"), py::arg("spe") = 0,
+        py::arg("ctr_advanced") = false, py::arg("head_blocks") = -1);
   m.def("read_stamps", &read_stamps);
   m.def("graph_upload", &graph_upload);
   register_comm(m);

@@ -368,6 +368,29 @@ void launch_f32_conv_bwd(const float* a1g, const float* xng, const float* dpool,
                          const uint8_t* pmask, const float* w2, int B, int ipb, float* slab,
                          bool x3, const float* w2x, hipStream_t st);
 
+// ---------------------------------------------------------------- MLP (mlp.hip)
+// 784 -> fc1 128 -> ReLU -> fc2 10 (--arch mlp): fc1's forward and weight gradient with the raw
+// uint8 image as one MFMA operand (exact in bf16) and the other as split-bf16 hi / lo planes;
+// the normalisation is folded out of both GEMMs (docs/kernels.md "MLP").  Everything behind
+// fc1's pre-activation is launch_cnn_head* / launch_cnn_predict_head.
+constexpr int MLP_IN = 784;
+// images / labels / nrow / ctr / sr as launch_f32_fwd (ctr == nullptr: rows 0 .. B - 1).
+// whi / wlo: fc1.weight [128][784] as bf16(w) and bf16(w - bf16(w)), row-major (the optimizer
+// keeps them current: OptSeg shadow / shadow_lo).  Writes ylab[B] (the label words verbatim)
+// and part [splitk][B][128] without bias, split s holding its k-steps' share of both halves
+// of the fold; splitk in {1, 5, 25}.
+void launch_mlp_fwd(const uint8_t* images, const int32_t* labels, int64_t nrow, const int64_t* ctr,
+                    StepRows sr, int B, const __bf16* whi, const __bf16* wlo, float* part,
+                    int32_t* ylab, int splitk, hipStream_t st);
+// gw1 [128][784] = the fc1 weight gradient of the step's B rows from dh32 [>= B][128] (the
+// head's fp32 dh; rows >= B are not read), in a fixed order; the rows are those of counter
+// *ctr - cback (the head between the forward and this launch advances the counter: cback = 1).
+// The same launch reduces the head's slabs (launch_f32_fc1_bwd's third role, same contract).
+void launch_mlp_bwd(const uint8_t* images, int64_t nrow, const int64_t* ctr, int64_t cback,
+                    StepRows sr, int B, const float* dh32, float* gw1, const float* head_slab,
+                    int head_blocks, float* gwf2, float* gbf2, float* gbf1, double* metrics,
+                    hipStream_t st);
+
 // ---------------------------------------------------------------- prediction (predict.hip)
 // The inference twins of cnn_head<eval> / lin_eval: per-row outputs instead of three sums.
 // logp fp32 [B][10] (log-softmax), pred int32 [B] (first maximum); optional: ylab / labels,

@@ -82,6 +82,8 @@ FILE_FLAGS = {
     "kernels/cnn_head.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
     "kernels/cnn_head_drop.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # its twin
     "kernels/cnn_head_mix.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],    # and its
+    # no packed fp32 VALU ops (v_pk_add / mul / fma_f32) in the MLP kernels' folds and splits
+    "kernels/mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

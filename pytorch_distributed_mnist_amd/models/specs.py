@@ -171,7 +171,18 @@ def cnn_spec() -> ModelSpec:
     ], num_buckets=2)
 
 
-SPECS = {"linear": linear_spec, "cnn": cnn_spec}
+def mlp_spec() -> ModelSpec:
+    # 784 -> 128 -> ReLU -> 10 (csrc/kernels/mlp.hip): torch layouts throughout (the kernels
+    # read fc1.weight [128][784] row-major), one bucket in backward-ready order
+    return ModelSpec("mlp", [
+        ParamSpec("fc2.weight", (10, 128), (10, 128), 2),
+        ParamSpec("fc2.bias", (10,), (10,), 3),
+        ParamSpec("fc1.bias", (128,), (128,), 1),
+        ParamSpec("fc1.weight", (128, 784), (128, 784), 0),
+    ], num_buckets=1)
+
+
+SPECS = {"linear": linear_spec, "cnn": cnn_spec, "mlp": mlp_spec}
 
 
 def get_spec(name: str) -> ModelSpec:

@@ -51,6 +51,12 @@ def make_gpu_step(prog, use_graphs: bool = True):
             raise ValueError(f"unsupported CNN dtype {prog.dtype!r} (bf16 or fp32)")
         from .cnn_step import CnnStep
         return CnnStep(prog, use_graphs)
+    if prog.model == "mlp":
+        if prog.dtype != "fp32":
+            raise ValueError("the MLP has one program, fp32 semantics on split-bf16 products "
+                             "(--dtype fp32)")
+        from .mlp_step import MlpStep
+        return MlpStep(prog, use_graphs)
     raise ValueError(prog.model)
 
 

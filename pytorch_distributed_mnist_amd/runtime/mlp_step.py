@@ -1,0 +1,144 @@
+"""MLP GPU step program (``--arch mlp``): 784 -> fc1 128 -> ReLU -> fc2 10, fp32 semantics.
+
+  mlp_fwd   split-K fc1 GEMM on the raw uint8 rows of the epoch buffer -> fp32 partials, ylab
+  cnn_head  fc1 reduce + bias + ReLU, fc2, CE, head backward (dh in fp32), counters -- the CNN
+            programs' head and its smoothing / dropout / mixup twins (launch_head_train)
+  mlp_bwd   dW1 tiles | head-slab reduction                         -> the one bucket complete
+  world size 1: optimizer;  world size > 1: all-reduce -> optimizer
+
+The image operand of both GEMMs is exact in bf16; fc1's weight goes in as hi / lo bf16 planes
+that the optimizer keeps current (``csrc/kernels/mlp.hip``, docs/kernels.md "MLP").
+"""
+from __future__ import annotations
+
+import torch
+
+from .gpu_step import GpuStepBase
+
+EVAL_CHUNK = 2048
+NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
+
+
+def mlp_splitk(b: int) -> int:
+    """Split-K of mlp_fwd for b rows: the 25 k-steps over 25, 5 or 1 workgroups per 16-row
+    m-tile, the most that keeps the launch within two rounds of the 256 CUs."""
+    mt = -(-b // 16)
+    for s in (25, 5):
+        if mt * s <= 512:
+            return s
+    return 1
+
+
+class MlpStep(GpuStepBase):
+    def __init__(self, prog, use_graphs):
+        super().__init__(prog, use_graphs)
+        C, dev, B = self.C, self.device, self.bfull
+        f32 = torch.float32
+        self.ldt = -(-B // 32) * 32
+        cap = max(B, EVAL_CHUNK)
+        self.ylab = torch.empty(cap, dtype=torch.int32, device=dev)
+        part_n = max(max(mlp_splitk(b) * b for b in range(1, B + 1)),
+                     mlp_splitk(EVAL_CHUNK) * EVAL_CHUNK) * 128
+        self.part = torch.empty(part_n, dtype=f32, device=dev)
+        self.dh32 = torch.zeros(self.ldt * 128, dtype=f32, device=dev)
+        self.head_slab = torch.empty(C.cnn_head_nblk(self.ldt) * C.CNN_HEAD_SLAB, dtype=f32,
+                                     device=dev)
+        a = self.arena
+        self.P = {n: a.param(n) for n in NAMES}
+        self.G = {n: a.grad(n) for n in NAMES}
+        # fc1.weight as split-bf16 planes [hi | lo], each [128][784] row-major
+        self.w1split = torch.empty(2 * 128 * 784, dtype=torch.bfloat16, device=dev)
+        self.refresh_shadows()
+
+    @torch.no_grad()
+    def refresh_shadows(self) -> None:
+        """Re-derive fc1.weight's hi / lo planes (hi = bf16(w), lo = bf16(w - hi)) from the fp32
+        master: the optimizer keeps them current after every update, this covers any other
+        change (construction, a re-broadcast)."""
+        self._split_w1(self.arena, self.w1split)
+
+    @staticmethod
+    def _split_w1(arena, out: torch.Tensor) -> torch.Tensor:
+        w = arena.param("fc1.weight").reshape(-1)
+        n = w.numel()
+        hi = w.to(torch.bfloat16)
+        out[:n].copy_(hi)
+        out[n:].copy_((w - hi.float()).to(torch.bfloat16))
+        return out
+
+    @torch.no_grad()
+    def weight_set(self, arena):
+        """(name views, fc1.weight's hi / lo planes) of `arena`; fresh tensors, the training
+        copy is not touched."""
+        return ({n: arena.param(n) for n in NAMES},
+                self._split_w1(arena, torch.empty_like(self.w1split)))
+
+    def optimizer_segments(self):
+        segs = []
+        for p in self.arena.spec.params:
+            off = self.arena.spec.offset(p.name)
+            if p.name == "fc1.weight":
+                n = p.numel
+                segs.append((off, 1, n, self.w1split[:n], None, None, None, None, None,
+                             self.w1split[n:]))
+            else:
+                segs.append((off, 1, p.numel, None, None))
+        return segs
+
+    def _fwd(self, images, labels, ctr, bfull, b, w1split, spe=0) -> int:
+        s = mlp_splitk(b)
+        n = 128 * 784
+        self.C.mlp_fwd(images, labels, ctr, bfull, b, w1split[:n], w1split[n:], self.part,
+                       self.ylab, s, spe=spe)
+        return s
+
+    def _train_impl(self, B: int) -> None:
+        C, P, G = self.C, self.P, self.G
+        ldt = -(-B // 32) * 32
+        images = self.ep_images.view(-1, 784)
+        s = self._fwd(images, self.ep_labels, self.ctr[0:1], self.bfull, B, self.w1split,
+                      spe=self.spe)
+        self.launch_head_train(self.part, s, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
+                               self.ylab, None, None, ldt, self.head_slab,
+                               self.metrics.train_view(), self.ctr[0:1], self.opt._step_dev, None,
+                               self.dh32)
+        # the head has advanced the data-step counter: the backward reads the rows of counter - 1
+        C.mlp_bwd(images, self.ctr[0:1], self.bfull, B, self.dh32, ldt, G["fc1.weight"],
+                  self.head_slab, G["fc2.weight"], G["fc2.bias"], G["fc1.bias"],
+                  self.metrics.train_view(), spe=self.spe, ctr_advanced=True)
+        red = self.reducer
+        if red.streamed:
+            # the optimizer publishes the bucket and waits for the persistent collective
+            self.launch_optimizer(signal_ch=0)
+            return
+        red.bucket_ready(0)
+        red.finalize()
+        self.launch_optimizer()
+
+    def evaluate(self, ws=None) -> None:
+        C = self.C
+        P, w1split = (self.P, self.w1split) if ws is None else ws
+        n = self.test_images.shape[0]
+        for s in range(0, n, EVAL_CHUNK):
+            b = min(EVAL_CHUNK, n - s)
+            se = self._fwd(self.test_images[s:s + b], self.test_labels[s:s + b], None, b, b,
+                           w1split)
+            C.cnn_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
+                       False, None, None, 32, None, self.metrics.eval_view(), None, None)
+
+    def predict(self, images_u8, labels=None, ws=None):
+        """evaluate()'s forward over any images, ending in the prediction head
+        (csrc/kernels/predict.hip) instead of the metric sums."""
+        C = self.C
+        P, w1split = (self.P, self.w1split) if ws is None else ws
+        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
+        n = images.shape[0]
+        # the forward copies its rows' labels to ylab either way: zeros without labels
+        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
+        for s in range(0, n, EVAL_CHUNK):
+            b = min(EVAL_CHUNK, n - s)
+            se = self._fwd(images[s:s + b], flab[s:s + b], None, b, b, w1split)
+            C.cnn_predict_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
+                               self.ylab if lab is not None else None, logp[s:s + b],
+                               pred[s:s + b], conf)
+        return logp, pred, conf

@@ -68,7 +68,7 @@ class TrainProgram:
         # of the whole training set, on the GPU inside the epoch gather (image) and the head
         # kernel (target), on the CPU per batch.  None or alpha = 0: off, and nothing changes.
         self.mixup = mixup if mixup is not None and mixup.enabled else None
-        if self.mixup is not None and model != "cnn":
+        if self.mixup is not None and model not in ("cnn", "mlp"):
             raise ValueError(f"mixup is built into the CNN's training head: the {model} model "
                              "has no such head")
         self._mix_table = self.mixup.table() if self.mixup is not None else None
@@ -94,7 +94,7 @@ class TrainProgram:
         # inside the head kernel, on the CPU a multiplier after fc1's ReLU.  None or p = 0: off,
         # and nothing changes.
         self.dropout = dropout if dropout is not None and dropout.enabled else None
-        if self.dropout is not None and model != "cnn":
+        if self.dropout is not None and model not in ("cnn", "mlp"):
             raise ValueError(f"dropout needs a hidden layer: the {model} model has none")
         # train-time augmentation (data/augment.py): applied to the training batches only --
         # on the GPU inside the epoch gather, on the CPU per batch.  None or a spec with every
@@ -251,7 +251,8 @@ class TrainProgram:
             return ("the weight average (--ema-decay) takes in every step's whole weights on "
                     "every rank")
         if self.model != "cnn":
-            return f"the {self.model} model has no fc1 layer to shard"
+            return (f"the {self.model} model has no fc1 layer to shard" if self.model == "linear"
+                    else f"the {self.model} program has no sharded fc1 update")
         if self.gpu is not None:
             if not hasattr(self.gpu, "shard_unsupported_reason"):
                 return (f"the {self.dtype} CNN program has no sharded update "

@@ -1,4 +1,5 @@
-"""Per-kernel timing of the CNN step kernels at several batch sizes (CUDA events)."""
+"""Per-kernel timing of the CNN step kernels at several batch sizes (CUDA events);
+`kbench.py mlp [B ...]`: the MLP's two kernels and its step."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -37,8 +38,35 @@ def timeit(fn, iters=50):
     return a.elapsed_time(b) / (3 * iters) * 1e3
 
 
+def mlp(sizes):
+    """mlp_fwd / mlp_bwd (csrc/kernels/mlp.hip) and the whole MLP step at each batch size."""
+    for B in sizes:
+        p = build_local_program("mlp", "fp32", "cuda", B, train, test, optimizer="sgd", lr=0.01,
+                                use_graphs=False)
+        p.optimizer.sync_hyperparams()
+        p.set_train_indices(distributed_indices(len(train), 1, 0, 0))
+        st = p.gpu
+        C, G = st.C, st.G
+        ldt = -(-B // 32) * 32
+        st.train_step(B)
+        torch.cuda.synchronize()
+        z = torch.zeros(1, dtype=torch.int64, device="cuda")
+        images = st.ep_images.view(-1, 784)
+        fwd = lambda: st._fwd(images, st.ep_labels, z, B, B, st.w1split, spe=st.spe)
+        bwd = lambda: C.mlp_bwd(images, z, B, B, st.dh32, ldt, G["fc1.weight"], st.head_slab,
+                                G["fc2.weight"], G["fc2.bias"], G["fc1.bias"],
+                                st.metrics.train_view(), spe=st.spe)
+        t = [(timeit(fwd), timeit(bwd)) for _ in range(3)]
+        st.ctr.zero_()
+        step = timeit(lambda: st._train_impl(B), 8)
+        print(f"mlp B={B:5d} S={fwd()} mlp_fwd|mlp_bwd x3: " +
+              " ".join(f"{a:.2f}|{b:.2f}" for a, b in t) +
+              f" | step={step:.1f}us -> {B / step:.2f}M img/s", flush=True)
+
 
 def main():
+  if sys.argv[1:2] == ["mlp"]:
+      return mlp([int(b) for b in (sys.argv[2:] or ["32", "256", "4096"])])
   for B in [int(b) for b in (sys.argv[1:] or ["256", "1024", "4096"])]:
       p = build_local_program("cnn", "bf16", "cuda", B, train, test, optimizer="sgd", lr=0.01,
                               use_graphs=False)

@@ -152,5 +152,23 @@ def main():
     print("window writes: avg LDS passes per wave-instruction %.2f (8 groups x 1 pass = 8 ideal)" % (tot/n))
 
 
+def mlp_bwd(pitch=144):
+    """mlp_bwd's transposed image tile ([16 pixels][128 rows] bytes, `pitch` bytes per pixel):
+    the staging byte writes (thread t: row t & 127, pixels 8 (t >> 7) + j; modelled as dword
+    accesses, like the 2-byte scatter above) and the ds_read_b64 fragment reads (lane (g, i16):
+    rows 32 ks + 8 g .. + 7 of pixel i16)."""
+    wt = wi = rt = ri = 0
+    for wave in range(4):
+        for j in range(8):
+            addrs = [(8 * (wave >> 1) + j) * pitch + (64 * (wave & 1) + l) for l in range(64)]
+            cy, idl = cycles(addrs, 'u16'); wt += cy; wi += idl
+    for ks in range(4):
+        addrs = [(l & 15) * pitch + 32 * ks + 8 * (l >> 4) for l in range(64)]
+        cy, idl = cycles(addrs, 'b64'); rt += cy; ri += idl
+    print("mlp_bwd pitch %d: byte writes %.2f | b64 fragment reads %.2f" % (pitch, wt / wi, rt / ri))
+
+
 if __name__ == "__main__":
+    for pitch in (128, 136, 144):
+        mlp_bwd(pitch)
     main()

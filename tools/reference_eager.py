@@ -40,7 +40,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_distributed_mnist_amd.data.mnist import synthetic_split  # noqa: E402
-from pytorch_distributed_mnist_amd.models.reference import CNN, Net  # noqa: E402
+from pytorch_distributed_mnist_amd.models.reference import CNN, MLP, Net  # noqa: E402
 
 
 class NormalizedMNIST(torch.utils.data.Dataset):
@@ -65,7 +65,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--batch", type=int, default=256, help="per-rank batch")
     ap.add_argument("--workers", type=int, default=4)
-    ap.add_argument("--model", choices=["cnn", "linear"], default="cnn")
+    ap.add_argument("--model", choices=["cnn", "linear", "mlp"], default="cnn")
     ap.add_argument("--optimizer", choices=["sgd", "adam"], default="sgd")
     ap.add_argument("--loader", choices=["dataloader", "device", "graph"], default="dataloader")
     ap.add_argument("--amp", choices=["none", "bf16"], default="none",
@@ -83,7 +83,7 @@ def main():
     dist.init_process_group("nccl", rank=rank, world_size=ws)
 
     torch.manual_seed(1234)
-    model = (CNN() if a.model == "cnn" else Net()).to(dev)
+    model = {"cnn": CNN, "linear": Net, "mlp": MLP}[a.model]().to(dev)
     if a.loader == "graph":
         return graph_loop(a, model, dev, rank, ws)
     model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank])
@@ -229,7 +229,7 @@ def graph_loop(a, model, dev, rank, ws):
     el = float(t.item())
     if rank == 0:
         print(json.dumps({
-            "what": "the same CNN step in PyTorch: device-resident data, whole step captured in "
+            "what": "the same " + a.model + " step in PyTorch: device-resident data, whole step captured in "
                     "a torch.cuda.graph" + (", bf16 autocast" if amp else ", fp32"),
             "model": a.model, "optimizer": a.optimizer, "loader": "graph", "amp": a.amp,
             "n_gpus": ws, "batch_per_rank": a.batch, "steps": a.steps, "warmup": a.warmup,

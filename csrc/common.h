@@ -165,6 +165,58 @@ __device__ __forceinline__ void pdm_bump_counters(int64_t* c0, int64_t* c1,
   }
 }
 
+// log-softmax CE on one row's logits (every lane's own registers); returns loss, writes softmax
+// probs, sets `correct` with torch.argmax tie-breaking (first maximal index).
+template <int N>
+__device__ __forceinline__ float row_xent(const float (&lg)[N], int y, float (&p)[N], int& correct) {
+  float m = lg[0];
+  int am = 0;
+#pragma unroll
+  for (int n = 1; n < N; ++n)
+    if (lg[n] > m) { m = lg[n]; am = n; }
+  float s = 0.f;
+#pragma unroll
+  for (int n = 0; n < N; ++n) { p[n] = expf(lg[n] - m); s += p[n]; }
+  const float lse = m + logf(s);
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int n = 0; n < N; ++n) p[n] *= inv;
+  correct = (am == y);
+  float ly = lg[0];
+#pragma unroll
+  for (int n = 1; n < N; ++n) ly = (n == y) ? lg[n] : ly;
+  return lse - ly;
+}
+
+// Log-softmax of one row's logits: lp = lg - lse with row_xent's max / expf / logf sequence;
+// returns the first maximal index and the row loss lse - lg[y] as row_xent forms it.
+template <int N>
+__device__ __forceinline__ int row_logp(const float (&lg)[N], int y, float (&lp)[N], float& loss) {
+  float m = lg[0];
+  int am = 0;
+#pragma unroll
+  for (int n = 1; n < N; ++n)
+    if (lg[n] > m) { m = lg[n]; am = n; }
+  float s = 0.f;
+#pragma unroll
+  for (int n = 0; n < N; ++n) s += expf(lg[n] - m);
+  const float lse = m + logf(s);
+#pragma unroll
+  for (int n = 0; n < N; ++n) lp[n] = lg[n] - lse;
+  float ly = lg[0];
+#pragma unroll
+  for (int n = 1; n < N; ++n) ly = (n == y) ? lg[n] : ly;
+  loss = lse - ly;
+  return am;
+}
+
+// confusion[y][am] += 1 over N classes; a label outside [0, N) counts nowhere (and writes nowhere)
+template <int N>
+__device__ __forceinline__ void count_confusion(int64_t* __restrict__ confusion, int y, int am) {
+  if ((unsigned)y < (unsigned)N)
+    atomicAdd(reinterpret_cast<unsigned long long*>(confusion) + y * N + am, 1ull);
+}
+
 // Label smoothing of the training heads (--label-smoothing E, torch's F.cross_entropy(...,
 // label_smoothing = E) over n classes): the target of class c is (1 - E) [c = y] + E / n, so
 //   dlogits_c = (softmax_c - t_c) / B,   row loss = lse - ((1 - E) l_y + E mean_c l_c)

@@ -392,7 +392,8 @@ void launch_mlp_bwd(const uint8_t* images, int64_t nrow, const int64_t* ctr, int
                     hipStream_t st);
 
 // ---------------------------------------------------------------- prediction (predict.hip)
-// The inference twins of cnn_head<eval> / lin_eval: per-row outputs instead of three sums.
+// The inference forms of cnn_head<eval> (the same head body, PREDICT) / lin_eval: per-row
+// outputs instead of three sums.
 // logp fp32 [B][10] (log-softmax), pred int32 [B] (first maximum); optional: ylab / labels,
 // and with them confusion int64 [10][10] (confusion[y][pred] += 1) and the evaluation head's
 // fp64 metrics[3] additions.  Rows >= B write nothing.

@@ -141,25 +141,4 @@ __device__ __forceinline__ bf16x8 cat_tr(s16x4 lo, s16x4 hi) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
-template <int N>
-__device__ __forceinline__ float row_xent(const float (&lg)[N], int y, float (&p)[N], int& correct) {
-  float m = lg[0];
-  int am = 0;
-#pragma unroll
-  for (int n = 1; n < N; ++n)
-    if (lg[n] > m) { m = lg[n]; am = n; }
-  float s = 0.f;
-#pragma unroll
-  for (int n = 0; n < N; ++n) { p[n] = expf(lg[n] - m); s += p[n]; }
-  const float lse = m + logf(s);
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int n = 0; n < N; ++n) p[n] *= inv;
-  correct = (am == y);
-  float ly = lg[0];
-#pragma unroll
-  for (int n = 1; n < N; ++n) ly = (n == y) ? lg[n] : ly;
-  return lse - ly;
-}
-
 }  // namespace cnn

@@ -1,6 +1,6 @@
 // Device helpers shared by the Linear-model kernels (linear.hip, predict.hip): the register
-// image of W, the uint8 -> normalised-float row staging, a wave's logits and the row
-// log-softmax CE.
+// image of W, the uint8 -> normalised-float row staging, a wave's logits (the row
+// log-softmax CE, row_xent, is common.h's).
 #pragma once
 #include "../common.h"
 #include "../kernels.h"
@@ -73,29 +73,6 @@ __device__ __forceinline__ void wave_logits(const float (*xs)[K], const int (&ro
   for (int i = 0; i < R; ++i)
 #pragma unroll
     for (int n = 0; n < N; ++n) lg[i][n] = wave_sum_dpp(acc[i][n]) + bias[n];
-}
-
-// log-softmax CE on one row's logits; returns loss, writes softmax probs, sets
-// `correct` with torch.argmax tie-breaking (first maximal index).
-__device__ __forceinline__ float row_xent(const float (&lg)[N], int y, float (&p)[N], int& correct) {
-  float m = lg[0];
-  int am = 0;
-#pragma unroll
-  for (int n = 1; n < N; ++n) {
-    if (lg[n] > m) { m = lg[n]; am = n; }
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int n = 0; n < N; ++n) { p[n] = expf(lg[n] - m); s += p[n]; }
-  const float lse = m + logf(s);
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int n = 0; n < N; ++n) p[n] *= inv;
-  correct = (am == y);
-  float ly = lg[0];
-#pragma unroll
-  for (int n = 1; n < N; ++n) ly = (n == y) ? lg[n] : ly;
-  return lse - ly;
 }
 
 }  // namespace lin

@@ -80,8 +80,8 @@ FILE_FLAGS = {
     "kernels/fc1_fwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "kernels/fc1_bwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "kernels/cnn_head.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
-    "kernels/cnn_head_drop.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # its twin
-    "kernels/cnn_head_mix.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],    # and its
+    "kernels/cnn_head_drop.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # the same
+    "kernels/cnn_head_mix.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],    # head body
     # no packed fp32 VALU ops (v_pk_add / mul / fma_f32) in the MLP kernels' folds and splits
     "kernels/mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }

@@ -43,8 +43,26 @@ def test_no_kernel_uses_scratch(kernels):
 def test_every_hot_kernel_is_present(kernels):
     for name in ("cnn_fwd_kernel", "fc1_fwd_kernel", "cnn_head_kernel", "fc1_bwd_kernel",
                  "cnn_bwd_kernel", "conv_reduce_kernel", "optim_kernel", "lin_train_kernel",
-                 "xgmi_allreduce_kernel", "cnn_fwd_band_kernel", "cnn_bwd_band_kernel"):
+                 "xgmi_allreduce_kernel", "cnn_fwd_band_kernel", "cnn_bwd_band_kernel",
+                 "cnn_head_smooth_kernel", "cnn_head_dropout_kernel", "cnn_head_mixup_kernel",
+                 "cnn_predict_head_kernel"):
         _find(kernels, name)
+
+
+def test_head_variants_allocate_their_own_lds_only(kernels):
+    """Every head kernel is an instance of one body (csrc/kernels/cnn_head_body.h).  The
+    training variants allocate its four arrays once -- hs 4*128*4 + dhs 4*128*4 + dls 4*10*4 +
+    red 4*2*4 = 4288 B -- and the evaluation and prediction heads red alone (32 B): a variant
+    that instantiated the training arrays by accident, or a second __shared__ block, shows
+    here."""
+    train = 4 * 128 * 4 + 4 * 128 * 4 + 4 * 10 * 4 + 4 * 2 * 4
+    assert train == 4288
+    want = {"cnn_head_kernelILb1E": train, "cnn_head_smooth_kernel": train,
+            "cnn_head_dropout_kernel": train, "cnn_head_mixup_kernel": train,
+            "cnn_head_kernelILb0E": 4 * 2 * 4, "cnn_predict_head_kernel": 4 * 2 * 4}
+    for name, lds in want.items():
+        for k, v in _find(kernels, name).items():
+            assert v["group_segment_fixed_size"] == lds, (k, v["group_segment_fixed_size"], lds)
 
 
 def test_occupancy_budgets(kernels):

@@ -109,7 +109,7 @@ def main():
           "cnn_head": lambda: C.cnn_head(st.part, S, B, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
                                          st.ylab, True, st.dh, st.dht, ldt, st.head_slab,
                                          st.metrics.train_view(), None, None),
-          # the head's masking twin at p = 0.5 (untagged labels: every row draws sample 0's
+          # the head's masking variant at p = 0.5 (untagged labels: every row draws sample 0's
           # mask, the same work)
           "cnn_head_dropout": lambda: C.cnn_head_dropout(st.part, S, B, P["fc1.bias"],
                                                          P["fc2.weight"], P["fc2.bias"], st.ylab,
@@ -122,7 +122,7 @@ def main():
                                                        st.dh, st.dht, ldt, st.head_slab,
                                                        st.metrics.train_view(), None, None, None,
                                                        None, 0.1),
-          # the masking head's two-class twin (--mixup 0.4, p = 0.5): the row's pair is drawn
+          # the masking head's two-class variant (--mixup 0.4, p = 0.5): the row's pair is drawn
           # from the label word (untagged: sample 0's pair in every row, the same work), the
           # partner's label read from the tagged training labels
           "cnn_head_mixup": lambda: C.cnn_head_mixup(st.part, S, B, P["fc1.bias"], P["fc2.weight"],
@@ -152,7 +152,7 @@ def main():
                           "cnn_head_sched", "ema", "ema_nt"):            # variants, opt-in launches
               tot += us
           line.append(f"{name}={us:.1f}")
-      # the mixup head against the head it is the twin of, interleaved
+      # the mixup head against the head it extends, interleaved
       pairs = [(timeit(ks["cnn_head_dropout"]), timeit(ks["cnn_head_mixup"])) for _ in range(4)]
       line.append("dropout|mixup x4: " + " ".join(f"{a:.2f}|{b:.2f}" for a, b in pairs))
       st.ctr.zero_()   # each step advances the data counter (rows are clamped past the epoch)

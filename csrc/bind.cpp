@@ -1323,9 +1323,15 @@ void mlp_fwd(at::Tensor images, at::Tensor labels, c10::optional<at::Tensor> ctr
 void mlp_bwd(at::Tensor images, c10::optional<at::Tensor> ctr, int64_t bfull, int64_t B,
              at::Tensor dh, int64_t ldt, at::Tensor gw1, at::Tensor head_slab, at::Tensor gwf2,
              at::Tensor gbf2, at::Tensor gbf1, at::Tensor metrics, int64_t spe,
-             bool ctr_advanced, int64_t head_blocks) {
+             bool ctr_advanced, int64_t head_blocks, c10::optional<at::Tensor> dh_colsum) {
   c10::DeviceGuard g(images.device());
   check_mlp_rows(images, ctr, bfull, B);
+  float* colsum = nullptr;
+  if (dh_colsum.has_value() && dh_colsum->defined()) {
+    need(*dh_colsum, at::kFloat, "dh_colsum");
+    TORCH_CHECK(dh_colsum->numel() == CNN_HID, "dh_colsum [128]");
+    colsum = dh_colsum->data_ptr<float>();
+  }
   TORCH_CHECK(ldt % 32 == 0 && ldt >= B, "ldt must be a multiple of 32 and >= B");
   need_min(dh, at::kFloat, ldt * CNN_HID, "dh32");
   need(gw1, at::kFloat, "gw1");
@@ -1347,7 +1353,47 @@ void mlp_bwd(at::Tensor images, c10::optional<at::Tensor> ctr, int64_t bfull, in
                  step_rows(bfull, ctr.has_value() ? spe : 0, images.size(0)), (int)B,
                  dh.data_ptr<float>(), gw1.data_ptr<float>(), head_slab.data_ptr<float>(), hb,
                  gwf2.data_ptr<float>(), gbf2.data_ptr<float>(), gbf1.data_ptr<float>(),
-                 metrics.data_ptr<double>(), cur_stream(images));
+                 metrics.data_ptr<double>(), cur_stream(images), colsum);
+}
+
+// ------------------------------------------------------------------ MLP, two hidden layers (mlp_hid.hip)
+static void check_mlp_hid_w(const at::Tensor& w2) {
+  need(w2, at::kFloat, "w2");
+  TORCH_CHECK(w2.numel() == (int64_t)CNN_HID * CNN_HID, "fc2 weight [128, 128]");
+  need_aligned(w2.data_ptr(), 16, "w2");
+}
+
+void mlp_hid_fwd(at::Tensor part, int64_t splitk, int64_t B, at::Tensor b1, at::Tensor w2,
+                 c10::optional<at::Tensor> h1, at::Tensor pre2, int64_t ngroups) {
+  c10::DeviceGuard g(part.device());
+  TORCH_CHECK(B >= 1 && B <= (1 << 24), "batch size");
+  TORCH_CHECK(splitk >= 1 && splitk <= 64, "splitk must be in 1..64, got ", splitk);
+  TORCH_CHECK(ngroups == 1 || ngroups == 2, "ngroups must be 1 or 2, got ", ngroups);
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need(b1, at::kFloat, "b1");
+  TORCH_CHECK(b1.numel() == CNN_HID, "fc1 bias [128]");
+  need_aligned(b1.data_ptr(), 8, "b1");
+  check_mlp_hid_w(w2);
+  const bool keep = h1.has_value() && h1->defined();      // the backward's copy (training)
+  if (keep) need_min(*h1, at::kFloat, B * CNN_HID, "h1");
+  need_min(pre2, at::kFloat, B * CNN_HID, "pre2");
+  launch_mlp_hid_fwd(part.data_ptr<float>(), (int)splitk, (int)B, b1.data_ptr<float>(),
+                     w2.data_ptr<float>(), keep ? h1->data_ptr<float>() : nullptr, pre2.data_ptr<float>(),
+                     (int)ngroups, cur_stream(part));
+}
+
+void mlp_hid_bwd(at::Tensor dh2, at::Tensor h1, at::Tensor w2, int64_t B, at::Tensor dh1,
+                 at::Tensor gw2) {
+  c10::DeviceGuard g(dh2.device());
+  TORCH_CHECK(B >= 1 && B <= (1 << 24), "batch size");
+  need_min(dh2, at::kFloat, B * CNN_HID, "dh32");
+  need_min(h1, at::kFloat, B * CNN_HID, "h1");
+  check_mlp_hid_w(w2);
+  need_min(dh1, at::kFloat, B * CNN_HID, "dh1");
+  need(gw2, at::kFloat, "gw2");
+  TORCH_CHECK(gw2.numel() == (int64_t)CNN_HID * CNN_HID, "fc2 grad [128, 128]");
+  launch_mlp_hid_bwd(dh2.data_ptr<float>(), h1.data_ptr<float>(), w2.data_ptr<float>(), (int)B,
+                     dh1.data_ptr<float>(), gw2.data_ptr<float>(), cur_stream(dh2));
 }
 
 // Upload an instantiated hipGraph (torch.cuda.CUDAGraph.raw_cuda_graph_exec()) to the device
@@ -1508,7 +1554,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("mlp_bwd", &mlp_bwd, py::arg("images"), py::arg("ctr"), py::arg("bfull"), py::arg("B"),
         py::arg("dh"), py::arg("ldt"), py::arg("gw1"), py::arg("head_slab"), py::arg("gwf2"),
         py::arg("gbf2"), py::arg("gbf1"), py::arg("metrics"), py::arg("spe") = 0,
-        py::arg("ctr_advanced") = false, py::arg("head_blocks") = -1);
+        py::arg("ctr_advanced") = false, py::arg("head_blocks") = -1,
+        py::arg("dh_colsum") = py::none());
+  m.attr("MLP_HID_ROUND") = MLP_HID_ROUND;
+  m.def("mlp_hid_fwd", &mlp_hid_fwd, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("b1"),
+        py::arg("w2"), py::arg("h1"), py::arg("pre2"), py::arg("ngroups") = 2);
+  m.def("mlp_hid_bwd", &mlp_hid_bwd, py::arg("dh2"), py::arg("h1"), py::arg("w2"), py::arg("B"),
+        py::arg("dh1"), py::arg("gw2"));
   m.def("read_stamps", &read_stamps);
   m.def("graph_upload", &graph_upload);
   register_comm(m);

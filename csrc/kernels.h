@@ -386,10 +386,29 @@ void launch_mlp_fwd(const uint8_t* images, const int32_t* labels, int64_t nrow, 
 // head's fp32 dh; rows >= B are not read), in a fixed order; the rows are those of counter
 // *ctr - cback (the head between the forward and this launch advances the counter: cback = 1).
 // The same launch reduces the head's slabs (launch_f32_fc1_bwd's third role, same contract).
+// dh_colsum (optional, [128]): the column sums sum_b dh32[b][n] the affine fold forms anyway,
+// stored by tile 0 (--arch mlp2: fc1's bias gradient; null: the kernel of --arch mlp as it was).
 void launch_mlp_bwd(const uint8_t* images, int64_t nrow, const int64_t* ctr, int64_t cback,
                     StepRows sr, int B, const float* dh32, float* gw1, const float* head_slab,
                     int head_blocks, float* gwf2, float* gbf2, float* gbf1, double* metrics,
-                    hipStream_t st);
+                    hipStream_t st, float* dh_colsum = nullptr);
+
+// ---------------------------------------------------------------- MLP, two hidden layers (mlp_hid.hip)
+// The 128 -> 128 layer of --arch mlp2 (784 -> 128 -> ReLU -> 128 -> ReLU -> 10) on the fp32
+// MFMA, between launch_mlp_fwd / launch_mlp_bwd and the head (docs/kernels.md "MLP, two hidden
+// layers").  w2 is the fp32 master fc2.weight [128][128] (torch layout: [out n][in k]).
+constexpr int MLP_HID_ROUND = 128;   // batch rows per round of the dW2 role
+// h1 [>= B][128] = relu(b1 + sum_s part[s]) (bias first, splits in order: the head's convention)
+// and pre2 [1][B][128] = h1 . w2^T without bias, a one-split partial for the head.  part is
+// launch_mlp_fwd's [splitk][B][128], any splitk >= 1.  Rows >= B of h1 are not written; h1 == nullptr (evaluation): not stored.
+// ngroups in {1, 2}: workgroups per 16-row m-tile, each computing 128 / ngroups output units.
+void launch_mlp_hid_fwd(const float* part, int splitk, int B, const float* b1, const float* w2,
+                        float* h1, float* pre2, int ngroups, hipStream_t st);
+// dh1 [>= B][128] = [h1 > 0] (dh2 . w2) and gw2 [128][128] = dh2^T . h1 over the B rows, in a
+// fixed order.  dh2 is the head's dh32; rows >= B of dh2 and h1 are never read and rows >= B of
+// dh1 are not written.
+void launch_mlp_hid_bwd(const float* dh2, const float* h1, const float* w2, int B, float* dh1,
+                        float* gw2, hipStream_t st);
 
 // ---------------------------------------------------------------- prediction (predict.hip)
 // The inference forms of cnn_head<eval> (the same head body, PREDICT) / lin_eval: per-row

@@ -135,11 +135,14 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(
 }
 
 // ------------------------------------------------------------------ mlp_bwd
+// COLSUM (--arch mlp2): tile 0 also stores the column sums of dh that the fold is made of
+template <bool COLSUM>
 __global__ __launch_bounds__(256) void mlp_bwd_kernel(
     const uint8_t* __restrict__ images, int64_t nrow, const int64_t* __restrict__ ctr, int64_t cback,
     StepRows sr, int B, const float* __restrict__ dh, float* __restrict__ gw1,
     const float* __restrict__ head_slab, int head_blocks, float* __restrict__ gwf2,
-    float* __restrict__ gbf2, float* __restrict__ gbf1, double* __restrict__ metrics) {
+    float* __restrict__ gbf2, float* __restrict__ gbf1, double* __restrict__ metrics,
+    float* __restrict__ dh_colsum) {
   __shared__ __attribute__((aligned(16))) char sm[2 * MB_BUF];
   const int bid = blockIdx.x;
   if (bid >= MB_TILES) {
@@ -206,7 +209,11 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     // sum_b dh[b][n], n = the D fragment's column; the lane's rows are pixels 4 g .. 4 g + 3
-    const float fold = MLP_BETA * sum_xor32(sum_xor16(rs[nt]));
+    const float cs = sum_xor32(sum_xor16(rs[nt]));
+    if constexpr (COLSUM) {
+      if (bid == 0 && g == 0) dh_colsum[wave * 32 + nt * 16 + i16] = cs;
+    }
+    const float fold = MLP_BETA * cs;
     const f32x4 o = {fmaf(MLP_ALPHA, acc[nt][0], -fold), fmaf(MLP_ALPHA, acc[nt][1], -fold),
                      fmaf(MLP_ALPHA, acc[nt][2], -fold), fmaf(MLP_ALPHA, acc[nt][3], -fold)};
     *reinterpret_cast<f32x4*>(gw1 + (int64_t)(wave * 32 + nt * 16 + i16) * MLP_K + px0 + 4 * g) = o;
@@ -230,7 +237,13 @@ void launch_mlp_fwd(const uint8_t* images, const int32_t* labels, int64_t nrow, 
 void launch_mlp_bwd(const uint8_t* images, int64_t nrow, const int64_t* ctr, int64_t cback,
                     StepRows sr, int B, const float* dh32, float* gw1, const float* head_slab,
                     int head_blocks, float* gwf2, float* gbf2, float* gbf1, double* metrics,
-                    hipStream_t st) {
-  mlp_bwd_kernel<<<MB_TILES + HRB, 256, 0, st>>>(images, nrow, ctr, cback, sr, B, dh32, gw1, head_slab,
-                                                head_blocks, gwf2, gbf2, gbf1, metrics);
+                    hipStream_t st, float* dh_colsum) {
+  if (dh_colsum != nullptr)
+    mlp_bwd_kernel<true><<<MB_TILES + HRB, 256, 0, st>>>(images, nrow, ctr, cback, sr, B, dh32, gw1,
+                                                         head_slab, head_blocks, gwf2, gbf2, gbf1,
+                                                         metrics, dh_colsum);
+  else
+    mlp_bwd_kernel<false><<<MB_TILES + HRB, 256, 0, st>>>(images, nrow, ctr, cback, sr, B, dh32, gw1,
+                                                          head_slab, head_blocks, gwf2, gbf2, gbf1,
+                                                          metrics, nullptr);
 }

@@ -87,9 +87,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help='seed for initializing training (applied inside every rank).')
     # ---- additions (opt-in; defaults reproduce the reference) ----
     g = parser.add_argument_group("MI355X framework options")
-    g.add_argument('--arch', choices=['linear', 'cnn', 'mlp'], default='linear',
+    g.add_argument('--arch', choices=['linear', 'cnn', 'mlp', 'mlp2'], default='linear',
                    help="linear = reference Net (Linear 784->10); cnn = north-star CNN; mlp = "
-                        "one hidden layer (784 -> 128 -> ReLU -> 10)")
+                        "one hidden layer (784 -> 128 -> ReLU -> 10); mlp2 = two hidden layers "
+                        "(784 -> 128 -> ReLU -> 128 -> ReLU -> 10)")
     g.add_argument('--optimizer', choices=['adam', 'sgd'], default='adam')
     g.add_argument('--dtype', choices=['auto', 'fp32', 'bf16'], default='auto',
                    help='compute dtype of activations / GEMM inputs (master weights stay fp32); '
@@ -158,7 +159,8 @@ def build_parser() -> argparse.ArgumentParser:
     # dropout on the CNN's hidden units (data/dropout.py; no defaults, as above: absent = 0 = off)
     g.add_argument('--dropout', metavar='P', type=_ranged(float, 0.0, 0.9),
                    default=argparse.SUPPRESS,
-                   help='--arch cnn / mlp: drop each of the 128 hidden units in front of fc2 with '
+                   help='--arch cnn / mlp / mlp2: drop each of the 128 hidden units in front of the '
+                        'output layer (fc2; mlp2: its second hidden layer, in front of fc3) with '
                         'probability P (0..0.9, default 0 = off) in training steps, kept units '
                         'scaled by 1 / (1 - P); evaluation never drops')
     g.add_argument('--dropout-seed', metavar='N', type=_ranged(int, 0, 2 ** 64 - 1),
@@ -193,7 +195,7 @@ def build_parser() -> argparse.ArgumentParser:
     # mixup (data/mixup.py; no defaults, as above: absent = 0 = off)
     g.add_argument('--mixup', metavar='A', type=_ranged(float, 0.0, 10.0),
                    default=argparse.SUPPRESS,
-                   help='--arch cnn / mlp: mixup (Zhang et al. 2018) in training steps: every sample is '
+                   help='--arch cnn / mlp / mlp2: mixup (Zhang et al. 2018) in training steps: every sample is '
                         'blended with a partner drawn from the whole training set, image and '
                         'target alike, with weight lambda ~ Beta(A, A) folded to >= 1/2 (0 < A '
                         '<= 10, default 0 = off); the printed train loss is the mixed loss, '
@@ -234,13 +236,16 @@ def parse_args(argv=None):
                      "the evaluation pass)")
     if getattr(args, "dropout", 0.0) > 0.0 and args.arch == "linear":
         parser.error("argument --dropout: --arch linear has no hidden layer to drop "
-                     "(use --arch cnn or mlp)")
+                     "(use --arch cnn, mlp or mlp2)")
     if getattr(args, "mixup", 0.0) > 0.0 and args.arch == "linear":
         parser.error("argument --mixup: only the CNN's training head mixes targets "
-                     "(use --arch cnn or mlp, which shares that head)")
+                     "(use --arch cnn, or mlp / mlp2, which share that head)")
     if args.arch == "mlp" and args.dtype == "bf16":
         parser.error("argument --dtype: --arch mlp has one program, fp32 semantics with its "
                      "products on the bf16 matrix cores (use --dtype auto or fp32)")
+    if args.arch == "mlp2" and args.dtype == "bf16":
+        parser.error("argument --dtype: --arch mlp2 has one program, fp32 semantics with its "
+                     "hidden layer on the fp32 matrix cores (use --dtype auto or fp32)")
     if hasattr(args, "lr_min") and getattr(args, "lr_schedule", "step") in ("step", "constant"):
         parser.error("argument --lr-min: --lr-schedule {} has no final rate (use --lr-schedule "
                      "linear or cosine)".format(getattr(args, "lr_schedule", "step")))

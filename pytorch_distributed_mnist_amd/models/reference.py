@@ -7,7 +7,8 @@
   MaxPool2d(2), flatten 9216 -> fc1 128 + ReLU -> fc2 10, trained with
   log-softmax + NLL (== ``F.cross_entropy`` on the logits, which is exactly what the
   reference's Trainer applies, ``multi_proc_single_gpu.py:88``).
-* ``MLP`` is the one-hidden-layer perceptron, 784 -> fc1 128 + ReLU -> fc2 10.
+* ``MLP`` is the one-hidden-layer perceptron, 784 -> fc1 128 + ReLU -> fc2 10, and ``MLP2``
+  the two-hidden-layer one, 784 -> fc1 128 + ReLU -> fc2 128 + ReLU -> fc3 10.
 
 These modules are used for three things only: (1) drawing the initial weights
 with torch's default initialisers so a seeded run matches a seeded reference run
@@ -59,12 +60,23 @@ class MLP(nn.Module):
         return self.fc2(F.relu(self.fc1(x.view(x.size(0), -1))))
 
 
+class MLP2(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.fc1 = nn.Linear(784, 128)
+        self.fc2 = nn.Linear(128, 128)
+        self.fc3 = nn.Linear(128, 10)
+
+    def forward(self, x):
+        return self.fc3(F.relu(self.fc2(F.relu(self.fc1(x.view(x.size(0), -1))))))
+
+
 def functional_forward(model_name: str, params: dict, x: torch.Tensor,
                        hidden_mult: torch.Tensor | None = None) -> torch.Tensor:
     """Forward of any model from a {torch_name: tensor} dict (torch layouts).  hidden_mult
-    (CNN and MLP, training only): a per-row multiplier [N, 128] applied after fc1's ReLU -- the dropout
-    mask times its keep scale (data/dropout.py)."""
-    if hidden_mult is not None and model_name not in ("cnn", "mlp"):
+    (CNN and MLPs, training only): a per-row multiplier [N, 128] applied after the last hidden
+    layer's ReLU (fc1's; mlp2: fc2's) -- the dropout mask times its keep scale (data/dropout.py)."""
+    if hidden_mult is not None and model_name not in ("cnn", "mlp", "mlp2"):
         raise ValueError(f"the {model_name} model has no hidden layer to drop")
     if model_name == "linear":
         return F.linear(x.reshape(x.size(0), -1), params["fc.weight"], params["fc.bias"])
@@ -83,7 +95,13 @@ def functional_forward(model_name: str, params: dict, x: torch.Tensor,
         if hidden_mult is not None:
             h = h * hidden_mult
         return F.linear(h, params["fc2.weight"], params["fc2.bias"])
+    if model_name == "mlp2":
+        h = F.relu(F.linear(x.reshape(x.size(0), -1), params["fc1.weight"], params["fc1.bias"]))
+        h = F.relu(F.linear(h, params["fc2.weight"], params["fc2.bias"]))
+        if hidden_mult is not None:
+            h = h * hidden_mult
+        return F.linear(h, params["fc3.weight"], params["fc3.bias"])
     raise ValueError(f"unknown model {model_name!r}")
 
 
-MODULES = {"linear": Net, "cnn": CNN, "mlp": MLP}
+MODULES = {"linear": Net, "cnn": CNN, "mlp": MLP, "mlp2": MLP2}

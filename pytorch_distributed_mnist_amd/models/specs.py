@@ -182,7 +182,21 @@ def mlp_spec() -> ModelSpec:
     ], num_buckets=1)
 
 
-SPECS = {"linear": linear_spec, "cnn": cnn_spec, "mlp": mlp_spec}
+def mlp2_spec() -> ModelSpec:
+    # 784 -> 128 -> ReLU -> 128 -> ReLU -> 10 (csrc/kernels/mlp.hip, mlp_hid.hip): torch layouts
+    # throughout (mlp_hid reads the fp32 fc2.weight [128][128] row-major), one bucket in
+    # backward-ready order
+    return ModelSpec("mlp2", [
+        ParamSpec("fc3.weight", (10, 128), (10, 128), 4),
+        ParamSpec("fc3.bias", (10,), (10,), 5),
+        ParamSpec("fc2.bias", (128,), (128,), 3),
+        ParamSpec("fc2.weight", (128, 128), (128, 128), 2),
+        ParamSpec("fc1.bias", (128,), (128,), 1),
+        ParamSpec("fc1.weight", (128, 784), (128, 784), 0),
+    ], num_buckets=1)
+
+
+SPECS = {"linear": linear_spec, "cnn": cnn_spec, "mlp": mlp_spec, "mlp2": mlp2_spec}
 
 
 def get_spec(name: str) -> ModelSpec:

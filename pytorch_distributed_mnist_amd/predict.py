@@ -51,7 +51,7 @@ class Predictor:
 def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
                    dtype: str = "auto", ema: bool = False, tta: int = 1,
                    augment: Optional[AugmentSpec] = None) -> Predictor:
-    """Build ``arch`` ("linear", "cnn" or "mlp") on ``device`` ("auto", "cuda" or "cpu") and load the
+    """Build ``arch`` ("linear", "cnn", "mlp" or "mlp2") on ``device`` ("auto", "cuda" or "cpu") and load the
     checkpoint's weights -- with ``ema=True`` its averaged weights (``ema_state_dict``, written
     by runs with ``--ema-decay``; a checkpoint without them raises KeyError).  A checkpoint of
     another architecture raises the arena's ``load_state_dict`` error.

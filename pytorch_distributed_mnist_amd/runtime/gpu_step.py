@@ -57,6 +57,12 @@ def make_gpu_step(prog, use_graphs: bool = True):
                              "(--dtype fp32)")
         from .mlp_step import MlpStep
         return MlpStep(prog, use_graphs)
+    if prog.model == "mlp2":
+        if prog.dtype != "fp32":
+            raise ValueError("the two-hidden-layer MLP has one program, fp32 semantics with its "
+                             "hidden layer on the fp32 MFMA (--dtype fp32)")
+        from .mlp2_step import Mlp2Step
+        return Mlp2Step(prog, use_graphs)
     raise ValueError(prog.model)
 
 

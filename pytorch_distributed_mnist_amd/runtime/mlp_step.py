@@ -30,6 +30,8 @@ def mlp_splitk(b: int) -> int:
 
 
 class MlpStep(GpuStepBase):
+    names = NAMES
+
     def __init__(self, prog, use_graphs):
         super().__init__(prog, use_graphs)
         C, dev, B = self.C, self.device, self.bfull
@@ -44,8 +46,8 @@ class MlpStep(GpuStepBase):
         self.head_slab = torch.empty(C.cnn_head_nblk(self.ldt) * C.CNN_HEAD_SLAB, dtype=f32,
                                      device=dev)
         a = self.arena
-        self.P = {n: a.param(n) for n in NAMES}
-        self.G = {n: a.grad(n) for n in NAMES}
+        self.P = {n: a.param(n) for n in self.names}
+        self.G = {n: a.grad(n) for n in self.names}
         # fc1.weight as split-bf16 planes [hi | lo], each [128][784] row-major
         self.w1split = torch.empty(2 * 128 * 784, dtype=torch.bfloat16, device=dev)
         self.refresh_shadows()
@@ -70,7 +72,7 @@ class MlpStep(GpuStepBase):
     def weight_set(self, arena):
         """(name views, fc1.weight's hi / lo planes) of `arena`; fresh tensors, the training
         copy is not touched."""
-        return ({n: arena.param(n) for n in NAMES},
+        return ({n: arena.param(n) for n in self.names},
                 self._split_w1(arena, torch.empty_like(self.w1split)))
 
     def optimizer_segments(self):

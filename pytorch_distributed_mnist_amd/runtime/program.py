@@ -68,7 +68,7 @@ class TrainProgram:
         # of the whole training set, on the GPU inside the epoch gather (image) and the head
         # kernel (target), on the CPU per batch.  None or alpha = 0: off, and nothing changes.
         self.mixup = mixup if mixup is not None and mixup.enabled else None
-        if self.mixup is not None and model not in ("cnn", "mlp"):
+        if self.mixup is not None and model not in ("cnn", "mlp", "mlp2"):
             raise ValueError(f"mixup is built into the CNN's training head: the {model} model "
                              "has no such head")
         self._mix_table = self.mixup.table() if self.mixup is not None else None
@@ -94,7 +94,7 @@ class TrainProgram:
         # inside the head kernel, on the CPU a multiplier after fc1's ReLU.  None or p = 0: off,
         # and nothing changes.
         self.dropout = dropout if dropout is not None and dropout.enabled else None
-        if self.dropout is not None and model not in ("cnn", "mlp"):
+        if self.dropout is not None and model not in ("cnn", "mlp", "mlp2"):
             raise ValueError(f"dropout needs a hidden layer: the {model} model has none")
         # train-time augmentation (data/augment.py): applied to the training batches only --
         # on the GPU inside the epoch gather, on the CPU per batch.  None or a spec with every

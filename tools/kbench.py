@@ -1,5 +1,6 @@
 """Per-kernel timing of the CNN step kernels at several batch sizes (CUDA events);
-`kbench.py mlp [B ...]`: the MLP's two kernels and its step."""
+`kbench.py mlp [B ...]`: the MLP's two kernels and its step; `kbench.py mlp2 [B ...]`: the
+two-hidden-layer MLP's hidden kernels (mlp_hid_fwd at both workgroup splits) and its step."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -9,6 +10,7 @@ from pytorch_distributed_mnist_amd.data.mnist import synthetic_split
 from pytorch_distributed_mnist_amd.data.sampler import distributed_indices
 from pytorch_distributed_mnist_amd.runtime.program import build_local_program
 from pytorch_distributed_mnist_amd.runtime.cnn_step import choose_bands, choose_ipb
+from pytorch_distributed_mnist_amd.runtime.mlp_step import mlp_splitk
 
 train = synthetic_split(60000, True)
 test = synthetic_split(512, False)
@@ -64,9 +66,35 @@ def mlp(sizes):
               f" | step={step:.1f}us -> {B / step:.2f}M img/s", flush=True)
 
 
+def mlp2(sizes):
+    """mlp_hid_fwd (1 and 2 workgroups per m-tile) / mlp_hid_bwd (csrc/kernels/mlp_hid.hip) and
+    the whole mlp2 step at each batch size."""
+    for B in sizes:
+        p = build_local_program("mlp2", "fp32", "cuda", B, train, test, optimizer="sgd", lr=0.01,
+                                use_graphs=False)
+        p.optimizer.sync_hyperparams()
+        p.set_train_indices(distributed_indices(len(train), 1, 0, 0))
+        st = p.gpu
+        C, P, G = st.C, st.P, st.G
+        st.train_step(B)
+        torch.cuda.synchronize()
+        S = mlp_splitk(B)
+        fwd = lambda g: C.mlp_hid_fwd(st.part, S, B, P["fc1.bias"], P["fc2.weight"], st.h1,
+                                      st.pre2, ngroups=g)
+        bwd = lambda: C.mlp_hid_bwd(st.dh32, st.h1, P["fc2.weight"], B, st.dh1, G["fc2.weight"])
+        t = [(timeit(lambda: fwd(1)), timeit(lambda: fwd(2)), timeit(bwd)) for _ in range(3)]
+        st.ctr.zero_()
+        step = timeit(lambda: st._train_impl(B), 8)
+        print(f"mlp2 B={B:5d} S={S} mlp_hid_fwd g=1|g=2|mlp_hid_bwd x3: " +
+              " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}" for a, b, c in t) +
+              f" | step={step:.1f}us -> {B / step:.2f}M img/s", flush=True)
+
+
 def main():
   if sys.argv[1:2] == ["mlp"]:
       return mlp([int(b) for b in (sys.argv[2:] or ["32", "256", "4096"])])
+  if sys.argv[1:2] == ["mlp2"]:
+      return mlp2([int(b) for b in (sys.argv[2:] or ["32", "256", "4096"])])
   for B in [int(b) for b in (sys.argv[1:] or ["256", "1024", "4096"])]:
       p = build_local_program("cnn", "bf16", "cuda", B, train, test, optimizer="sgd", lr=0.01,
                               use_graphs=False)

@@ -168,7 +168,24 @@ def mlp_bwd(pitch=144):
     print("mlp_bwd pitch %d: byte writes %.2f | b64 fragment reads %.2f" % (pitch, wt / wi, rt / ri))
 
 
+def mlp_hid_fwd(pitch=136):
+    """mlp_hid_fwd's h1 tile ([16 rows][128 units] fp32, `pitch` dwords per row): the phase-1
+    ds_write_b64 (thread t: row t >> 4, units 2 (t & 15) + 32 j) and the phase-2 ds_read_b128 A
+    fragments (lane (g, i16): units 16 q + 4 g .. + 3 of row i16)."""
+    wt = wi = rt = ri = 0
+    for wave in range(4):
+        for j in range(4):
+            addrs = [4 * ((4 * wave + (l >> 4)) * pitch + 2 * (l & 15) + 32 * j) for l in range(64)]
+            cy, idl = cycles(addrs, 'w64'); wt += cy; wi += idl
+    for q in range(8):
+        addrs = [4 * ((l & 15) * pitch + 16 * q + 4 * (l >> 4)) for l in range(64)]
+        cy, idl = cycles(addrs, 'b128'); rt += cy; ri += idl
+    print("mlp_hid_fwd pitch %d dwords: b64 writes %.2f | b128 fragment reads %.2f" % (pitch, wt / wi, rt / ri))
+
+
 if __name__ == "__main__":
+    for pitch in (128, 132, 136, 144):
+        mlp_hid_fwd(pitch)
     for pitch in (128, 136, 144):
         mlp_bwd(pitch)
     main()

@@ -13,6 +13,10 @@ bf16 MFMA (``conv_x3``, see below) or exactly on the fp32 MFMA (``v_mfma_f32_16x
   f32_conv_bwd conv2 dgrad + relu' + conv1 wgrad, conv2 wgrad       -> conv slabs
   world_size 1: optimizer with the conv slab reduction fused in
   world_size>1: conv_reduce -> all-reduce (both buckets) -> optimizer
+
+Evaluation and prediction are GpuStepBase's (gpu_step.py): per chunk of EVAL_CHUNK images,
+_eval_forward below -- f32_fwd (nothing kept for a backward) -> f32_fc1_fwd -- then cnn_head or
+cnn_predict_head.
 """
 from __future__ import annotations
 
@@ -20,10 +24,9 @@ import os
 
 import torch
 
-from .gpu_step import GpuStepBase
+from .gpu_step import EVAL_CHUNK, GpuStepBase, split_bf16
 from .structure import StepStructure
 
-EVAL_CHUNK = 2048
 SPLITK_TRAIN = 32        # fc1 split-K (divides 288: whole 32-float k chunks per split)
 
 
@@ -109,23 +112,14 @@ class CnnStepF32(GpuStepBase):
         """Re-derive the split-bf16 copy of conv2's weight (hi = bf16(w), lo = bf16(w - hi))
         from the fp32 master: the optimizer keeps it current after every update, this covers
         any other change (construction, a re-broadcast)."""
-        self._split_w2(self.arena, self.w2split)
-
-    @staticmethod
-    def _split_w2(arena, out: torch.Tensor) -> torch.Tensor:
-        w = arena.param("conv2.weight").reshape(-1)
-        n = w.numel()
-        hi = w.to(torch.bfloat16)
-        out[:n].copy_(hi)
-        out[n:].copy_((w - hi.float()).to(torch.bfloat16))
-        return out
+        split_bf16(self.arena.param("conv2.weight"), self.w2split)
 
     @torch.no_grad()
     def weight_set(self, arena):
         """(name views, conv2's weight as hi / lo planes) of `arena`; fresh tensors, the
         training copy is not touched."""
         return ({n: arena.param(n) for n in self.P},
-                self._split_w2(arena, torch.empty_like(self.w2split)))
+                split_bf16(arena.param("conv2.weight"), torch.empty_like(self.w2split)))
 
     def _seg(self, p, slab=None):
         """Optimizer segment of parameter p; conv2's weight also writes its hi / lo copy."""
@@ -190,39 +184,11 @@ class CnnStepF32(GpuStepBase):
         red.finalize()
         self.launch_optimizer()
 
-    def evaluate(self, ws=None) -> None:
-        C = self.C
+    def _eval_forward(self, images, labels, b, ws):
+        C, se = self.C, splitk_eval(b)
         P, w2split = (self.P, self.w2split) if ws is None else ws
-        n = self.test_images.shape[0]
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            se = splitk_eval(b)
-            C.f32_fwd(self.test_images[s:s + b], self.test_labels[s:s + b], None, b, b,
-                      P["conv1.weight"], P["conv1.bias"], P["conv2.weight"], P["conv2.bias"],
-                      self.pool, None, None, None, self.ylab, x3=self.conv_x3,
-                      w2s=w2split)
-            C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
-            C.cnn_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
-                       False, None, None, 32, None, self.metrics.eval_view(), None, None)
-
-    def predict(self, images_u8, labels=None, ws=None):
-        """evaluate()'s forward chain over any images, ending in the prediction head
-        (csrc/kernels/predict.hip) instead of the metric sums."""
-        C = self.C
-        P, w2split = (self.P, self.w2split) if ws is None else ws
-        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
-        n = images.shape[0]
-        # the forward copies its rows' labels to ylab either way: zeros without labels
-        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            se = splitk_eval(b)
-            C.f32_fwd(images[s:s + b], flab[s:s + b], None, b, b,
-                      P["conv1.weight"], P["conv1.bias"], P["conv2.weight"], P["conv2.bias"],
-                      self.pool, None, None, None, self.ylab, x3=self.conv_x3,
-                      w2s=w2split)
-            C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
-            C.cnn_predict_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
-                               self.ylab if lab is not None else None, logp[s:s + b],
-                               pred[s:s + b], conf)
-        return logp, pred, conf
+        C.f32_fwd(images, labels, None, b, b, P["conv1.weight"], P["conv1.bias"],
+                  P["conv2.weight"], P["conv2.bias"], self.pool, None, None, None, self.ylab,
+                  x3=self.conv_x3, w2s=w2split)
+        C.f32_fc1_fwd(self.pool, P["fc1.weight"], self.part, b, se, x3=self.conv_x3)
+        return self.part, se, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"]

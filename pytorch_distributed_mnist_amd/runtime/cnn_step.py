@@ -18,8 +18,9 @@ Kernel chain of one training step (compute stream; all-reduces on the RCCL strea
   optim(fc)    after bucket 0 -- inside a multi-step graph deferred to after the next
                step's cnn_fwd, which overlaps the 4.7 MB fc all-reduce
 
-Evaluation runs cnn_fwd (no activations kept) -> fc1_fwd -> cnn_head over the
-whole test set in chunks of EVAL_CHUNK images.
+Evaluation and prediction are GpuStepBase's (gpu_step.py): per chunk of EVAL_CHUNK images,
+_eval_forward below -- cnn_fwd (no activations kept) -> fc1_fwd -- then cnn_head or
+cnn_predict_head.
 """
 from __future__ import annotations
 
@@ -27,9 +28,7 @@ import os
 
 import torch
 
-from .gpu_step import GpuStepBase
-
-EVAL_CHUNK = 2048
+from .gpu_step import EVAL_CHUNK, GpuStepBase
 
 
 def frag_major(w: torch.Tensor) -> torch.Tensor:
@@ -705,37 +704,10 @@ class CnnStep(GpuStepBase):
         return ({n: arena.param(n) for n in self.P}, frag_major(w2.to(bf16)),
                 frag_major(w1.to(bf16)))
 
-    def evaluate(self, ws=None) -> None:
-        C = self.C
+    def _eval_forward(self, images, labels, b, ws):
+        C, S = self.C, self.splitk_eval
         P, w2, wf1 = (self.P, self.w2, self.wf1) if ws is None else ws
-        n = self.test_images.shape[0]
-        S = self.splitk_eval
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            C.cnn_fwd(self.test_images[s:s + b], self.test_labels[s:s + b], None, None, b, b,
-                      P["conv1.weight"], P["conv1.bias"], w2, P["conv2.bias"], self.pool,
-                      self.pmask, None, self.ylab)
-            C.fc1_fwd(self.pool, wf1, self.part, b, S)
-            C.cnn_head(self.part, S, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
-                       False, None, None, 32, None, self.metrics.eval_view(), None, None)
-
-    def predict(self, images_u8, labels=None, ws=None):
-        """evaluate()'s forward chain over any images, ending in the prediction head
-        (csrc/kernels/predict.hip) instead of the metric sums."""
-        C = self.C
-        P, w2, wf1 = (self.P, self.w2, self.wf1) if ws is None else ws
-        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
-        n = images.shape[0]
-        # the forward copies its rows' labels to ylab either way: zeros without labels
-        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
-        S = self.splitk_eval
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            C.cnn_fwd(images[s:s + b], flab[s:s + b], None, None, b, b,
-                      P["conv1.weight"], P["conv1.bias"], w2, P["conv2.bias"], self.pool,
-                      self.pmask, None, self.ylab)
-            C.fc1_fwd(self.pool, wf1, self.part, b, S)
-            C.cnn_predict_head(self.part, S, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
-                               self.ylab if lab is not None else None, logp[s:s + b],
-                               pred[s:s + b], conf)
-        return logp, pred, conf
+        C.cnn_fwd(images, labels, None, None, b, b, P["conv1.weight"], P["conv1.bias"], w2,
+                  P["conv2.bias"], self.pool, self.pmask, None, self.ylab)
+        C.fc1_fwd(self.pool, wf1, self.part, b, S)
+        return self.part, S, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"]

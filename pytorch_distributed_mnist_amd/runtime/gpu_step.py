@@ -20,6 +20,11 @@ ema_update, which only reads the optimizer-step counter.
 Linear (reference Net, fp32):  lin_train -> [lin_reduce -> all-reduce] -> optim
 CNN (bf16):  cnn_fwd -> fc1_fwd -> cnn_head -> fc1_bwd -> [all-reduce bucket 0]
              -> cnn_bwd -> conv_reduce -> [all-reduce bucket 1] -> optim
+
+Evaluation and prediction of the programs that end in the partial-sum head (both CNNs, both
+MLPs) are written once, in GpuStepBase: the rows in chunks of EVAL_CHUNK, the program's forward
+per chunk (its ``_eval_forward`` hook), then cnn_head or cnn_predict_head.  Linear has no
+partials: one lin_eval / lin_predict launch over all rows, its own two methods.
 """
 from __future__ import annotations
 
@@ -36,6 +41,20 @@ from .. import knobs
 _GRAPH_STEPS = int(knobs.get("PDM_GRAPH_STEPS", "16"))  # steps per full graph
 if _GRAPH_STEPS <= 0:
     raise ValueError(f"PDM_GRAPH_STEPS must be positive, got {_GRAPH_STEPS}")
+
+# rows per forward of evaluate() / predict(); the programs size their eval buffers for it
+EVAL_CHUNK = 2048
+
+
+def split_bf16(w: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The split-bf16 planes of an fp32 weight: hi = bf16(w) to out[:n], lo = bf16(w - hi) to
+    out[n:] (out: bf16 [2 n])."""
+    w = w.reshape(-1)
+    n = w.numel()
+    hi = w.to(torch.bfloat16)
+    out[:n].copy_(hi)
+    out[n:].copy_((w - hi.float()).to(torch.bfloat16))
+    return out
 
 
 def make_gpu_step(prog, use_graphs: bool = True):
@@ -192,54 +211,45 @@ class GpuStepBase:
         buf[0].copy_(idx)
         return buf
 
+    @staticmethod
+    def _gather_kw(tables, shift: int, epoch: int, seed: int) -> dict:
+        """The keywords every transforming gather takes: the Q14 tables, the shift range and
+        the (seed, epoch) of the draws; one workgroup per 64 rows, as the plain gather."""
+        cosq, sinq, invz = tables
+        return dict(max_wgs=0, cosq=cosq, sinq=sinq, invz=invz, shift=shift, epoch=epoch,
+                    seed=seed)
+
     def _gather(self, idx: torch.Tensor, half: int, stream, epoch=None) -> torch.cuda.Event:
         """Queue the gather of an epoch order into half `half` of the epoch buffer on `stream`;
         returns the event behind it.  With augmentation on, the augmenting gather draws the
         transforms of epoch `epoch`."""
         n = self._n_epoch
         buf = self._stage(idx)
+        a, m = self.augment, self.mixup
+        args = (self.train_images, self.train_labels, buf[0],
+                self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
+                self.ep_labels[half * n:(half + 1) * n])
         with torch.cuda.stream(stream):
-            if self.mixup is not None:
-                # --mixup: always the mixup twin of the elastic gather; without augmentation
-                # its ranges are zero (the identity tables), which is the plain mixed gather
-                a = self.augment
-                cosq, sinq, invz = self._aug_tables
-                self.C.gather_epoch_mixup(self.train_images, self.train_labels, buf[0],
-                                          self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
-                                          self.ep_labels[half * n:(half + 1) * n],
-                                          max_wgs=0, cosq=cosq, sinq=sinq, invz=invz,
-                                          shift=0 if a is None else a.shift, epoch=int(epoch),
-                                          seed=0 if a is None else a.seed,
-                                          elastic_q=0 if a is None else a.elastic_q,
-                                          qt=self._mix_table,
-                                          ntrain=self.train_images.shape[0],
-                                          mixup_seed=self.mixup.seed)
-            elif self.augment is None:
-                self.C.gather_epoch(self.train_images, self.train_labels, buf[0],
-                                    self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
-                                    self.ep_labels[half * n:(half + 1) * n],
-                                    # one workgroup per 64 rows (grid-striding ones taking
-                                    # fewer CUs beside the steps measured no better)
-                                    max_wgs=0)
-            elif self.augment.elastic > 0.0:
-                # --aug-elastic: the elastic twin of the augmenting gather (the same contract,
-                # plus the control displacements' range)
-                cosq, sinq, invz = self._aug_tables
-                self.C.gather_epoch_elastic(self.train_images, self.train_labels, buf[0],
-                                            self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
-                                            self.ep_labels[half * n:(half + 1) * n],
-                                            max_wgs=0, cosq=cosq, sinq=sinq, invz=invz,
-                                            shift=self.augment.shift, epoch=int(epoch),
-                                            seed=self.augment.seed,
-                                            elastic_q=self.augment.elastic_q)
+            if m is None and a is None:
+                # one workgroup per 64 rows (grid-striding ones taking fewer CUs beside the
+                # steps measured no better)
+                self.C.gather_epoch(*args, max_wgs=0)
             else:
-                cosq, sinq, invz = self._aug_tables
-                self.C.gather_epoch_augment(self.train_images, self.train_labels, buf[0],
-                                            self.ep_images.view(-1, 784)[half * n:(half + 1) * n],
-                                            self.ep_labels[half * n:(half + 1) * n],
-                                            max_wgs=0, cosq=cosq, sinq=sinq, invz=invz,
-                                            shift=self.augment.shift, epoch=int(epoch),
-                                            seed=self.augment.seed)
+                # (mixup without augmentation: zero ranges and the identity tables)
+                shift, seed, elastic_q = (0, 0, 0) if a is None else (a.shift, a.seed, a.elastic_q)
+                kw = self._gather_kw(self._aug_tables, shift, int(epoch), seed)
+                if m is not None:
+                    # --mixup: always the mixup twin of the elastic gather; without
+                    # augmentation that is the plain mixed gather
+                    self.C.gather_epoch_mixup(*args, elastic_q=elastic_q, qt=self._mix_table,
+                                              ntrain=self.train_images.shape[0],
+                                              mixup_seed=m.seed, **kw)
+                elif a.elastic > 0.0:
+                    # --aug-elastic: the elastic twin of the augmenting gather (the same
+                    # contract, plus the control displacements' range)
+                    self.C.gather_epoch_elastic(*args, elastic_q=elastic_q, **kw)
+                else:
+                    self.C.gather_epoch_augment(*args, **kw)
             ev = torch.cuda.Event()
             ev.record(stream)
         buf[1] = ev
@@ -677,11 +687,43 @@ class GpuStepBase:
                               float(self.reducer.grad_scale), segs, bump=bump, metrics=metrics,
                               **xg)
 
+    def _update_one_bucket(self) -> None:
+        """The end of a step whose gradients are one bucket: all-reduce it, update everything."""
+        red = self.reducer
+        if red.streamed:
+            # the optimizer publishes the bucket and waits for the persistent collective
+            self.launch_optimizer(signal_ch=0)
+            return
+        red.bucket_ready(0)
+        red.finalize()
+        self.launch_optimizer()
+
     def invalidate_graphs(self) -> None:
         self.graphs.clear()
         self._opt_segments = None
 
-    # -- prediction --------------------------------------------------------------
+    # -- evaluation and prediction -------------------------------------------------
+    def _eval_forward(self, images, labels, b: int, ws):
+        """The program's forward of b <= EVAL_CHUNK rows up to the fc partials, with the weight
+        set `ws` (None: the training weights); leaves the rows' label words in self.ylab and
+        returns what the head takes: (part, splitk, bf1, wf2, bf2)."""
+        raise NotImplementedError
+
+    def _forward_chunks(self, images, labels, ws):
+        """_eval_forward over the rows in chunks of EVAL_CHUNK: (start, rows, head arguments)
+        per chunk, each to be consumed before the next forward overwrites the buffers."""
+        n = images.shape[0]
+        for s in range(0, n, EVAL_CHUNK):
+            b = min(EVAL_CHUNK, n - s)
+            yield s, b, self._eval_forward(images[s:s + b], labels[s:s + b], b, ws)
+
+    def evaluate(self, ws=None) -> None:
+        """Add the test split's sums (loss, correct, rows) to the evaluation metrics."""
+        for _, b, (part, splitk, bf1, wf2, bf2) in \
+                self._forward_chunks(self.test_images, self.test_labels, ws):
+            self.C.cnn_head(part, splitk, b, bf1, wf2, bf2, self.ylab, False, None, None, 32,
+                            None, self.metrics.eval_view(), None, None)
+
     def _predict_io(self, images_u8: torch.Tensor, labels):
         """Device inputs and fresh outputs of ``predict``: (images uint8 [N, 784], labels int32
         [N] or None, log_probs fp32 [N, 10], pred int32 [N], confusion int64 [10, 10] or None).
@@ -705,10 +747,20 @@ class GpuStepBase:
         conf = None if lab is None else torch.zeros(10, 10, dtype=torch.int64, device=dev)
         return images, lab, logp, pred, conf
 
-    def predict(self, images_u8: torch.Tensor, labels=None):
+    def predict(self, images_u8: torch.Tensor, labels=None, ws=None):
         """(log_probs, pred, confusion | None) of any N >= 1 images, on the device; enqueued on
-        the current stream (the caller synchronises before reading)."""
-        raise NotImplementedError
+        the current stream (the caller synchronises before reading).  evaluate()'s forward
+        chain, ending in the prediction head (csrc/kernels/predict.hip) instead of the metric
+        sums."""
+        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
+        # the forward copies its rows' labels to ylab either way: zeros without labels
+        flab = lab if lab is not None else \
+            torch.zeros(images.shape[0], dtype=torch.int32, device=self.device)
+        for s, b, (part, splitk, bf1, wf2, bf2) in self._forward_chunks(images, flab, ws):
+            self.C.cnn_predict_head(part, splitk, b, bf1, wf2, bf2,
+                                    self.ylab if lab is not None else None, logp[s:s + b],
+                                    pred[s:s + b], conf)
+        return logp, pred, conf
 
     # -- test-time augmentation ----------------------------------------------------
     # rows per view gather and reduce launch: the whole 10,000-image test split in one (the
@@ -747,9 +799,7 @@ class GpuStepBase:
             scratch = (torch.zeros(n, dtype=torch.int32, device=dev),
                        torch.empty(b, dtype=torch.int32, device=dev))
         idx = torch.arange(start, start + b, dtype=torch.int32, device=dev)
-        cosq, sinq, invz = self._tta_tables(spec)
-        kw = dict(max_wgs=0, cosq=cosq, sinq=sinq, invz=invz, shift=spec.shift,
-                  epoch=TTA_EPOCH + v, seed=spec.seed)
+        kw = self._gather_kw(self._tta_tables(spec), spec.shift, TTA_EPOCH + v, spec.seed)
         if spec.elastic > 0.0:
             self.C.gather_epoch_elastic(images, scratch[0], idx, out, scratch[1],
                                         elastic_q=spec.elastic_q, **kw)
@@ -840,13 +890,7 @@ class LinearStep(GpuStepBase):
             return
         C.lin_reduce(self.slab, B, self.gW, self.gb, self.ctr[0:1],
                      red.sync if red.streamed else None, self.metrics.train_view())
-        if red.streamed:
-            # the optimizer publishes the bucket and waits for the persistent collective
-            self.launch_optimizer(signal_ch=0)
-            return
-        red.bucket_ready(0)
-        red.finalize()
-        self.launch_optimizer()
+        self._update_one_bucket()
 
     def weight_set(self, arena):
         return arena.param("fc.weight"), arena.param("fc.bias")

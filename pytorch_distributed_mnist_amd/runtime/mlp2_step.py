@@ -13,14 +13,18 @@ ReLU -> fc3 10, fp32 semantics.
 
 The hidden layer runs on the fp32 MFMA from the fp32 master weight (``csrc/kernels/mlp_hid.hip``,
 docs/kernels.md "MLP, two hidden layers"): no shadow planes beyond fc1.weight's.
+
+Evaluation and prediction are GpuStepBase's (gpu_step.py): per chunk of EVAL_CHUNK images,
+_eval_forward below -- mlp_fwd -> mlp_hid_fwd, h1 not kept -- then cnn_head or cnn_predict_head
+on pre2.
 """
 from __future__ import annotations
 
 import torch
 
+from .gpu_step import EVAL_CHUNK
 from .mlp_step import MlpStep
 
-EVAL_CHUNK = 2048
 NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias")
 
 
@@ -65,39 +69,10 @@ class Mlp2Step(MlpStep):
                   self.head_slab, G["fc3.weight"], G["fc3.bias"], G["fc2.bias"],
                   self.metrics.train_view(), spe=self.spe, ctr_advanced=True,
                   dh_colsum=G["fc1.bias"])
-        red = self.reducer
-        if red.streamed:
-            # the optimizer publishes the bucket and waits for the persistent collective
-            self.launch_optimizer(signal_ch=0)
-            return
-        red.bucket_ready(0)
-        red.finalize()
-        self.launch_optimizer()
+        self._update_one_bucket()
 
-    def evaluate(self, ws=None) -> None:
+    def _eval_forward(self, images, labels, b, ws):
         ws = (self.P, self.w1split) if ws is None else ws
         P = ws[0]
-        n = self.test_images.shape[0]
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            self._fwd2(self.test_images[s:s + b], self.test_labels[s:s + b], None, b, b, ws, None)
-            self.C.cnn_head(self.pre2, 1, b, P["fc2.bias"], P["fc3.weight"], P["fc3.bias"],
-                            self.ylab, False, None, None, 32, None, self.metrics.eval_view(), None,
-                            None)
-
-    def predict(self, images_u8, labels=None, ws=None):
-        """evaluate()'s forward over any images, ending in the prediction head
-        (csrc/kernels/predict.hip) instead of the metric sums."""
-        ws = (self.P, self.w1split) if ws is None else ws
-        P = ws[0]
-        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
-        n = images.shape[0]
-        # the forward copies its rows' labels to ylab either way: zeros without labels
-        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            self._fwd2(images[s:s + b], flab[s:s + b], None, b, b, ws, None)
-            self.C.cnn_predict_head(self.pre2, 1, b, P["fc2.bias"], P["fc3.weight"],
-                                    P["fc3.bias"], self.ylab if lab is not None else None,
-                                    logp[s:s + b], pred[s:s + b], conf)
-        return logp, pred, conf
+        self._fwd2(images, labels, None, b, b, ws, None)
+        return self.pre2, 1, P["fc2.bias"], P["fc3.weight"], P["fc3.bias"]

@@ -8,14 +8,16 @@
 
 The image operand of both GEMMs is exact in bf16; fc1's weight goes in as hi / lo bf16 planes
 that the optimizer keeps current (``csrc/kernels/mlp.hip``, docs/kernels.md "MLP").
+
+Evaluation and prediction are GpuStepBase's (gpu_step.py): per chunk of EVAL_CHUNK images,
+_eval_forward below -- mlp_fwd -- then cnn_head or cnn_predict_head.
 """
 from __future__ import annotations
 
 import torch
 
-from .gpu_step import GpuStepBase
+from .gpu_step import EVAL_CHUNK, GpuStepBase, split_bf16
 
-EVAL_CHUNK = 2048
 NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
 
 
@@ -57,23 +59,14 @@ class MlpStep(GpuStepBase):
         """Re-derive fc1.weight's hi / lo planes (hi = bf16(w), lo = bf16(w - hi)) from the fp32
         master: the optimizer keeps them current after every update, this covers any other
         change (construction, a re-broadcast)."""
-        self._split_w1(self.arena, self.w1split)
-
-    @staticmethod
-    def _split_w1(arena, out: torch.Tensor) -> torch.Tensor:
-        w = arena.param("fc1.weight").reshape(-1)
-        n = w.numel()
-        hi = w.to(torch.bfloat16)
-        out[:n].copy_(hi)
-        out[n:].copy_((w - hi.float()).to(torch.bfloat16))
-        return out
+        split_bf16(self.arena.param("fc1.weight"), self.w1split)
 
     @torch.no_grad()
     def weight_set(self, arena):
         """(name views, fc1.weight's hi / lo planes) of `arena`; fresh tensors, the training
         copy is not touched."""
         return ({n: arena.param(n) for n in self.names},
-                self._split_w1(arena, torch.empty_like(self.w1split)))
+                split_bf16(arena.param("fc1.weight"), torch.empty_like(self.w1split)))
 
     def optimizer_segments(self):
         segs = []
@@ -108,39 +101,9 @@ class MlpStep(GpuStepBase):
         C.mlp_bwd(images, self.ctr[0:1], self.bfull, B, self.dh32, ldt, G["fc1.weight"],
                   self.head_slab, G["fc2.weight"], G["fc2.bias"], G["fc1.bias"],
                   self.metrics.train_view(), spe=self.spe, ctr_advanced=True)
-        red = self.reducer
-        if red.streamed:
-            # the optimizer publishes the bucket and waits for the persistent collective
-            self.launch_optimizer(signal_ch=0)
-            return
-        red.bucket_ready(0)
-        red.finalize()
-        self.launch_optimizer()
+        self._update_one_bucket()
 
-    def evaluate(self, ws=None) -> None:
-        C = self.C
+    def _eval_forward(self, images, labels, b, ws):
         P, w1split = (self.P, self.w1split) if ws is None else ws
-        n = self.test_images.shape[0]
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            se = self._fwd(self.test_images[s:s + b], self.test_labels[s:s + b], None, b, b,
-                           w1split)
-            C.cnn_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"], self.ylab,
-                       False, None, None, 32, None, self.metrics.eval_view(), None, None)
-
-    def predict(self, images_u8, labels=None, ws=None):
-        """evaluate()'s forward over any images, ending in the prediction head
-        (csrc/kernels/predict.hip) instead of the metric sums."""
-        C = self.C
-        P, w1split = (self.P, self.w1split) if ws is None else ws
-        images, lab, logp, pred, conf = self._predict_io(images_u8, labels)
-        n = images.shape[0]
-        # the forward copies its rows' labels to ylab either way: zeros without labels
-        flab = lab if lab is not None else torch.zeros(n, dtype=torch.int32, device=self.device)
-        for s in range(0, n, EVAL_CHUNK):
-            b = min(EVAL_CHUNK, n - s)
-            se = self._fwd(images[s:s + b], flab[s:s + b], None, b, b, w1split)
-            C.cnn_predict_head(self.part, se, b, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"],
-                               self.ylab if lab is not None else None, logp[s:s + b],
-                               pred[s:s + b], conf)
-        return logp, pred, conf
+        se = self._fwd(images, labels, None, b, b, w1split)
+        return self.part, se, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"]

@@ -15,7 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import pytorch_distributed_mnist_amd.runtime.mlp_step as mlp_step
+import pytorch_distributed_mnist_amd.runtime.gpu_step as gpu_step
 from test_gpu_app import EPOCH_RE, cli
 from pytorch_distributed_mnist_amd.data.dropout import DropoutSpec, keep_mask
 from pytorch_distributed_mnist_amd.data.mixup import MixupSpec
@@ -206,8 +206,12 @@ def test_graphs_equal_eager_and_predict(gpu, monkeypatch):
     near = int(((top2[:, 0] - top2[:, 1]) < 1e-3).sum())      # (the two heads may split a tie)
     assert tl.count == len(y) and abs(nll - tl.sum) <= 1e-6 * tl.sum, (nll, tl.sum)
     assert near <= len(y) // 100 and abs(int(p.confusion.trace()) - ta.correct) <= near
-    monkeypatch.setattr(mlp_step, "EVAL_CHUNK", 8)
-    q = prog.predict(test.images[:21], test.labels[:21])
+    monkeypatch.setattr(gpu_step, "EVAL_CHUNK", 8)
+    rows, hook = [], prog.gpu._eval_forward
+    with monkeypatch.context() as m:
+        m.setattr(prog.gpu, "_eval_forward", lambda *a: rows.append(a[2]) or hook(*a))
+        q = prog.predict(test.images[:21], test.labels[:21])
+    assert rows == [8, 8, 5]              # three forwards: the patched chunk size was the loop's
     tp = {k: v.to(D) for k, v in prog.arena.torch_tensors(prog.arena.params).items()}
     ref = F.log_softmax(functional_forward("mlp", tp, normalize_reference(test.images[:21]).to(D)), 1)
     assert rel(q.log_probs.to(D), ref) < 1e-4

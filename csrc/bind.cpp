@@ -1356,6 +1356,53 @@ void mlp_bwd(at::Tensor images, c10::optional<at::Tensor> ctr, int64_t bfull, in
                  metrics.data_ptr<double>(), cur_stream(images), colsum);
 }
 
+// ------------------------------------------------------------------ MLP attack (mlp_attack.hip)
+void mlp_attack(at::Tensor part, int64_t splitk, int64_t B, at::Tensor ylab, at::Tensor b1,
+                at::Tensor w2, at::Tensor b2, at::Tensor whi, at::Tensor wlo, at::Tensor x0,
+                at::Tensor x, at::Tensor out, int64_t eps, int64_t alpha,
+                c10::optional<at::Tensor> grad, int64_t px_blocks) {
+  c10::DeviceGuard g(part.device());
+  TORCH_CHECK(B >= 1 && B <= (1 << 24), "batch size");
+  TORCH_CHECK(splitk == 1 || splitk == 5 || splitk == 25, "splitk must be 1, 5 or 25, got ", splitk);
+  TORCH_CHECK(eps >= 0 && eps <= 255, "eps must be in 0..255 grey levels, got ", eps);
+  TORCH_CHECK(alpha >= 1 && alpha <= 255, "alpha must be in 1..255 grey levels, got ", alpha);
+  TORCH_CHECK(px_blocks == 0 || px_blocks == 1 || px_blocks == 7, "px_blocks must be 0, 1 or 7, got ",
+              px_blocks);
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need_aligned(part.data_ptr(), 8, "part");
+  need_min(ylab, at::kInt, B, "ylab");
+  need(b1, at::kFloat, "b1");
+  need(w2, at::kFloat, "w2");
+  need(b2, at::kFloat, "b2");
+  TORCH_CHECK(b1.numel() == CNN_HID && w2.numel() == CNN_NCLS * CNN_HID && b2.numel() == CNN_NCLS,
+              "fc1 bias [128], fc2 weight [10, 128], fc2 bias [10]");
+  need_aligned(b1.data_ptr(), 8, "b1");
+  need_aligned(w2.data_ptr(), 8, "w2");
+  need(whi, at::kBFloat16, "whi");
+  need(wlo, at::kBFloat16, "wlo");
+  TORCH_CHECK(whi.numel() == (int64_t)CNN_HID * MLP_IN && wlo.numel() == whi.numel(),
+              "fc1 weight planes [128, 784]");
+  for (const void* q : {whi.data_ptr(), wlo.data_ptr()}) need_aligned(q, 16, "fc1 weight plane");
+  for (const at::Tensor* t : {&x0, &x, &out}) {
+    need(*t, at::kByte, "x0 / x / out");
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == MLP_IN && t->size(0) >= B, "x0 / x / out [>= B, 784]");
+    need_aligned(t->data_ptr(), 4, "x0 / x / out");
+  }
+  TORCH_CHECK(out.data_ptr() != x.data_ptr() && out.data_ptr() != x0.data_ptr(),
+              "out must not be x or x0");
+  float* gp = nullptr;
+  if (grad.has_value() && grad->defined()) {
+    need_min(*grad, at::kFloat, B * MLP_IN, "grad");
+    need_aligned(grad->data_ptr(), 16, "grad");
+    gp = grad->data_ptr<float>();
+  }
+  launch_mlp_attack(part.data_ptr<float>(), (int)splitk, (int)B, ylab.data_ptr<int32_t>(),
+                    b1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(),
+                    ptr<__bf16>(whi), ptr<__bf16>(wlo), x0.data_ptr<uint8_t>(),
+                    x.data_ptr<uint8_t>(), out.data_ptr<uint8_t>(), gp, (int)eps, (int)alpha,
+                    (int)px_blocks, cur_stream(part));
+}
+
 // ------------------------------------------------------------------ MLP, two hidden layers (mlp_hid.hip)
 static void check_mlp_hid_w(const at::Tensor& w2) {
   need(w2, at::kFloat, "w2");
@@ -1557,6 +1604,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ctr_advanced") = false, py::arg("head_blocks") = -1,
         py::arg("dh_colsum") = py::none());
   m.attr("MLP_HID_ROUND") = MLP_HID_ROUND;
+  m.def("mlp_attack", &mlp_attack, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("ylab"),
+        py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("whi"), py::arg("wlo"), py::arg("x0"),
+        py::arg("x"), py::arg("out"), py::arg("eps"), py::arg("alpha"), py::arg("grad") = py::none(),
+        py::arg("px_blocks") = 0);
   m.def("mlp_hid_fwd", &mlp_hid_fwd, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("b1"),
         py::arg("w2"), py::arg("h1"), py::arg("pre2"), py::arg("ngroups") = 2);
   m.def("mlp_hid_bwd", &mlp_hid_bwd, py::arg("dh2"), py::arg("h1"), py::arg("w2"), py::arg("B"),

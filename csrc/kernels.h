@@ -393,6 +393,22 @@ void launch_mlp_bwd(const uint8_t* images, int64_t nrow, const int64_t* ctr, int
                     int head_blocks, float* gwf2, float* gbf2, float* gbf1, double* metrics,
                     hipStream_t st, float* dh_colsum = nullptr);
 
+// ---------------------------------------------------------------- MLP attack (mlp_attack.hip)
+// One FGSM / PGD step of --arch mlp on raw bytes (docs/kernels.md "Adversarial evaluation"):
+// from launch_mlp_fwd's part [splitk][B][128] and ylab of the iterate x [B][784], with fc1's
+// bias, fc2 and fc1's hi / lo planes,
+//   g   = d(-log_softmax(logits(x))[y]) / d(normalised pixel)        per sample, no 1 / B
+//   out = clamp(x + alpha sign(g), max(0, x0 - eps), min(255, x0 + eps)),  sign(0) = 0
+// eps in 0..255 (0: out = x0), alpha in 1..255, grey levels.  grad (optional, fp32 [B][784]):
+// g itself.  x0, x and out are [B][784] bytes, 4-B aligned, out distinct from both.  Nothing
+// else is written: no counter, no metric.  px_blocks in {1, 7}: workgroups per 16-row m-tile,
+// each walking 7 / px_blocks rounds of 112 pixels; 0: MLP_ATTACK_PX_BLOCKS.
+constexpr int MLP_ATTACK_PX_BLOCKS = 7;
+void launch_mlp_attack(const float* part, int splitk, int B, const int32_t* ylab, const float* bf1,
+                       const float* wf2, const float* bf2, const __bf16* whi, const __bf16* wlo,
+                       const uint8_t* x0, const uint8_t* x, uint8_t* out, float* grad, int eps,
+                       int alpha, int px_blocks, hipStream_t st);
+
 // ---------------------------------------------------------------- MLP, two hidden layers (mlp_hid.hip)
 // The 128 -> 128 layer of --arch mlp2 (784 -> 128 -> ReLU -> 128 -> ReLU -> 10) on the fp32
 // MFMA, between launch_mlp_fwd / launch_mlp_bwd and the head (docs/kernels.md "MLP, two hidden

@@ -275,13 +275,27 @@ def run(args):
             test_loss, test_acc = trainer.evaluate()
             out('test loss: {}, test acc: {}.'.format(test_loss, test_acc))
             predict_out = getattr(args, "predict_out", None)
+            adv = None
+            if getattr(args, "attack_eps", 0) > 0:
+                # adversarial evaluation (--attack-eps, --arch mlp): every rank attacks the whole
+                # test split, as it evaluates it, and predicts the attacked images
+                from .runtime.cpu_step import check_attack
+                from .utils.metrics import Accuracy, Average
+                eps, steps, alpha = check_attack(args.attack_eps, getattr(args, "attack_steps", 1),
+                                                 getattr(args, "attack_alpha", None))
+                y = test_split.labels.to(torch.int64)
+                adv = program.predict(program.attack(eps=eps, steps=steps, alpha=alpha), y)
+                nll = -adv.log_probs.gather(1, y[:, None]).to(torch.float64).sum()
+                out('adversarial (eps {}/255, {} steps, alpha {}/255) loss: {}, acc: {}.'.format(
+                    eps, steps, alpha, Average.from_sums(float(nll), len(y)),
+                    Accuracy.from_counts(int(adv.pred.eq(y).sum()), len(y))))
             if predict_out:
                 # every rank runs the (unsharded) pass, as it runs the evaluation; rank 0 writes
                 # the file and prints the per-class lines
                 from .predict import class_lines, save_predictions
                 pred = program.predict()
                 if rank == 0:
-                    save_predictions(predict_out, pred, test_split.labels)
+                    save_predictions(predict_out, pred, test_split.labels, adv)
                     for line in class_lines(pred.confusion):
                         out(line)
             return

@@ -14,7 +14,8 @@ Additions are opt-in and default to the reference's behaviour:
 dropout on the CNN's hidden layer, ``--dropout`` / ``--dropout-seed``, the per-step learning-rate schedule
 ``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
 ``--label-smoothing``, mixup, ``--mixup`` / ``--mixup-seed``, the exponential moving average of the weights, ``--ema-decay`` /
-``--ema-warmup``, and test-time augmentation, ``--tta``.
+``--ema-warmup``, test-time augmentation, ``--tta``, and adversarial evaluation of ``--arch mlp``,
+``--attack-eps`` / ``--attack-steps`` / ``--attack-alpha``.
 """
 from __future__ import annotations
 
@@ -224,6 +225,22 @@ def build_parser() -> argparse.ArgumentParser:
                         'off; V > 1 needs an --aug-* range). Training is unchanged. Like --lr, it '
                         'is given again on --resume and --evaluate, which then reads the --aug-* '
                         'flags as the ranges of the views')
+    # adversarial evaluation (csrc/kernels/mlp_attack.hip; no defaults, as above: absent = off)
+    g.add_argument('--attack-eps', metavar='L', type=_ranged(int, 0, 255),
+                   default=argparse.SUPPRESS,
+                   help='--evaluate --arch mlp: after the test line, attack every test image '
+                        'within L grey levels (0..255, default 0 = off) up the plain loss of its '
+                        'label -- FGSM (Goodfellow et al. 2015) at one step, PGD without random '
+                        'start (Madry et al. 2018) at more -- and print the loss and accuracy on '
+                        'the attacked images; with --predict-out the file also holds '
+                        'adv_log_probs, adv_pred and adv_confusion')
+    g.add_argument('--attack-steps', metavar='K', type=_ranged(int, 1, 100),
+                   default=argparse.SUPPRESS,
+                   help='with --attack-eps: the number of attack steps (1..100, default 1)')
+    g.add_argument('--attack-alpha', metavar='A', type=_ranged(int, 1, 255),
+                   default=argparse.SUPPRESS,
+                   help='with --attack-eps: the step in grey levels (1..255; default L at one '
+                        'step, else max(1, round(2.5 L / K)))')
     parser.set_defaults(local_rank_given=False)
     return parser
 
@@ -256,6 +273,20 @@ def parse_args(argv=None):
         parser.error("argument --tta: {} views need a range to be drawn from (give --aug-shift, "
                      "--aug-rotate, --aug-zoom or --aug-elastic): without one every view is the "
                      "same image".format(args.tta))
+    attack = getattr(args, "attack_eps", 0) > 0
+    for flag in ("attack_steps", "attack_alpha"):
+        if hasattr(args, flag) and not attack:
+            parser.error("argument --{}: there is no attack to shape (give --attack-eps "
+                         "L)".format(flag.replace("_", "-")))
+    if attack and not args.evaluate:
+        parser.error("argument --attack-eps: the attack is an evaluation of a trained model "
+                     "(use it with --evaluate --resume)")
+    if attack and args.arch != "mlp":
+        parser.error("argument --attack-eps: --arch {} has no input-gradient kernel (only --arch "
+                     "mlp has one)".format(args.arch))
+    if attack and getattr(args, "tta", 1) > 1:
+        parser.error("argument --attack-eps: the attack is made on the image itself, not on "
+                     "--tta views (drop one of the two)")
     if hasattr(args, "ema_warmup") and not getattr(args, "ema_decay", 0.0):
         parser.error("argument --ema-warmup: there is no average to warm up (give --ema-decay D)")
     return args

@@ -47,6 +47,13 @@ class Predictor:
         augment=spec)``) log_probs is the log of the mean probability over the V views."""
         return self.program.predict(images, labels)
 
+    def attack(self, images, labels, eps: int, steps: int = 1, alpha=None) -> torch.Tensor:
+        """Adversarial images (``--arch mlp`` only): FGSM (steps = 1) or PGD without random start
+        within ``eps`` grey levels (0..255) of ``images`` (as ``predict``'s), ``steps`` steps of
+        ``alpha`` grey levels (None: eps at one step, else max(1, round(2.5 eps / steps))) up the
+        loss of ``labels``.  uint8 [N, 784] on the host; ``predict`` takes them as they are."""
+        return self.program.attack(images, labels, eps, steps, alpha)
+
 
 def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
                    dtype: str = "auto", ema: bool = False, tta: int = 1,
@@ -83,9 +90,12 @@ def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
     return Predictor(program)
 
 
-def save_predictions(path: str, prediction: Prediction, labels) -> None:
+def save_predictions(path: str, prediction: Prediction, labels,
+                     adversarial: Optional[Prediction] = None) -> None:
     """Write ``path`` (a NumPy .npz with log_probs, pred, labels, confusion) atomically:
-    temporary file in the same directory, then ``os.replace``, as checkpoints are."""
+    temporary file in the same directory, then ``os.replace``, as checkpoints are.  With
+    ``adversarial`` (the prediction on the attacked images, ``--attack-eps``) the file also
+    holds adv_log_probs, adv_pred and adv_confusion."""
     import os
     import tempfile
     d = os.path.dirname(path) or "."
@@ -95,7 +105,11 @@ def save_predictions(path: str, prediction: Prediction, labels) -> None:
         with os.fdopen(fd, "wb") as f:
             np.savez(f, log_probs=prediction.log_probs.numpy(), pred=prediction.pred.numpy(),
                      labels=torch.as_tensor(labels).to(torch.int64).cpu().numpy(),
-                     confusion=prediction.confusion.numpy())
+                     confusion=prediction.confusion.numpy(),
+                     **({} if adversarial is None else {
+                         "adv_log_probs": adversarial.log_probs.numpy(),
+                         "adv_pred": adversarial.pred.numpy(),
+                         "adv_confusion": adversarial.confusion.numpy()}))
         os.replace(tmp, path)
     except BaseException:
         if os.path.exists(tmp):

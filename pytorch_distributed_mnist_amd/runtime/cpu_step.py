@@ -105,6 +105,45 @@ def predict_step_cpu(model: str, arena, images_u8, labels=None):
     return log_probs, pred, confusion
 
 
+def check_attack(eps, steps, alpha):
+    """(eps, steps, alpha) of an attack as ints: eps in 0..255 grey levels (0 returns the images),
+    steps in 1..100, alpha in 1..255 or None for the default, eps at one step (FGSM), else
+    max(1, round(2.5 eps / steps)) (PGD, Madry et al. 2018)."""
+    eps, steps = int(eps), int(steps)
+    if not 0 <= eps <= 255:
+        raise ValueError(f"eps must be in 0..255 grey levels, got {eps}")
+    if not 1 <= steps <= 100:
+        raise ValueError(f"steps must be in 1..100, got {steps}")
+    if alpha is None:
+        alpha = max(1, eps if steps == 1 else int(2.5 * eps / steps + 0.5))
+    alpha = int(alpha)
+    if not 1 <= alpha <= 255:
+        raise ValueError(f"alpha must be in 1..255 grey levels, got {alpha}")
+    return eps, steps, alpha
+
+
+def attack_step_cpu(model: str, arena, images_u8, labels, eps: int, steps: int, alpha: int):
+    """FGSM / PGD on raw bytes (the CPU twin of csrc/kernels/mlp_attack.hip): `steps` times from
+    x = x0 = images_u8 (uint8 [N, 784]),
+        x = clamp(x + alpha sign(g), max(0, x0 - eps), min(255, x0 + eps)),   sign(0) = 0,
+    g the autograd gradient of the per-sample plain NLL of `labels` with respect to the normalised
+    pixels (the normalisation's slope is positive: the sign with respect to the byte).  uint8
+    [N, 784]."""
+    eps, steps, alpha = check_attack(eps, steps, alpha)
+    views = {p.name: p.to_torch(arena.param(p.name)).detach() for p in arena.spec.params}
+    x0 = images_u8.to(torch.int16)
+    lo, hi = (x0 - eps).clamp_(min=0), (x0 + eps).clamp_(max=255)
+    x = x0
+    y = labels.to(torch.int64)
+    for _ in range(steps):
+        with torch.enable_grad():
+            xn = normalize_reference(x.to(torch.uint8)).requires_grad_(True)
+            loss = F.cross_entropy(functional_forward(model, views, xn), y, reduction="sum")
+            g, = torch.autograd.grad(loss, xn)
+        x = torch.minimum(torch.maximum(x + alpha * torch.sign(g).to(torch.int16).view_as(x), lo), hi)
+    return x.to(torch.uint8)
+
+
 @torch.no_grad()
 def tta_reduce_cpu(logp_views, labels=None):
     """Test-time augmentation's combination (the CPU twin and oracle of csrc/kernels/tta.hip):

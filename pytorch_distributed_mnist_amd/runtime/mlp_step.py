@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import torch
 
+from .cpu_step import check_attack
 from .gpu_step import EVAL_CHUNK, GpuStepBase, split_bf16
 
 NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
@@ -107,3 +108,46 @@ class MlpStep(GpuStepBase):
         P, w1split = (self.P, self.w1split) if ws is None else ws
         se = self._fwd(images, labels, None, b, b, w1split)
         return self.part, se, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"]
+
+    @torch.no_grad()
+    def attack(self, images_u8: torch.Tensor, labels, eps: int, steps: int, alpha: int, ws=None,
+               chunk=None) -> torch.Tensor:
+        """The FGSM / PGD images of uint8 [N >= 1, 784] under the plain NLL of `labels`: uint8
+        [N, 784] on the device, within `eps` grey levels of the input, after `steps` steps of
+        `alpha` grey levels from the images themselves (csrc/kernels/mlp_attack.hip; docs/kernels.md
+        "Adversarial evaluation").  Per chunk of `chunk` rows (default and at most EVAL_CHUNK) and
+        step: mlp_fwd on the iterate, then mlp_attack, the iterates in two ping-pong buffers.
+        ws: the weight set attacked (None: the training weights).  Allocates, so not inside a
+        graph capture; nothing of the training step is touched."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("attack() allocates its buffers: call it outside a graph capture")
+        eps, steps, alpha = check_attack(eps, steps, alpha)
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 2 or images_u8.shape[1] != 784 \
+                or images_u8.shape[0] < 1:
+            raise ValueError("attack() takes uint8 images [N >= 1, 784], got "
+                             f"{images_u8.dtype} {tuple(images_u8.shape)}")
+        dev = self.device
+        images = images_u8.to(dev).contiguous()
+        n = images.shape[0]
+        if labels is None or labels.numel() != n:
+            raise ValueError(f"attack() needs one label per image ({n})")
+        lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+        chunk = EVAL_CHUNK if chunk is None else int(chunk)
+        if not 1 <= chunk <= EVAL_CHUNK:
+            raise ValueError(f"chunk must be in 1..{EVAL_CHUNK}, got {chunk}")
+        P, w1split = (self.P, self.w1split) if ws is None else ws
+        nw = 128 * 784
+        out = torch.empty_like(images)
+        pp = [torch.empty(min(chunk, n), 784, dtype=torch.uint8, device=dev) for _ in range(2)]
+        for s in range(0, n, chunk):
+            b = min(chunk, n - s)
+            x0 = cur = images[s:s + b]
+            for k in range(steps):
+                dst = out[s:s + b] if k == steps - 1 else pp[k & 1][:b]
+                se = self._fwd(cur, lab[s:s + b], None, b, b, w1split)
+                self.C.mlp_attack(self.part, se, b, self.ylab, P["fc1.bias"], P["fc2.weight"],
+                                  P["fc2.bias"], w1split[:nw], w1split[nw:], x0, cur, dst, eps,
+                                  alpha)
+                cur = dst
+        return out
+

@@ -29,7 +29,8 @@ from ..data.sampler import batch_bounds
 from ..optim.ema import EmaSpec, WeightEma
 from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
-from .cpu_step import eval_step_cpu, predict_step_cpu, train_step_cpu, tta_reduce_cpu
+from .cpu_step import (attack_step_cpu, check_attack, eval_step_cpu, predict_step_cpu,
+                       train_step_cpu, tta_reduce_cpu)
 from .structure import StepStructure
 
 
@@ -406,6 +407,42 @@ class TrainProgram:
                 for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)]
         return Prediction(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
                           None if labels is None else sum(o[2] for o in outs))
+
+    def attack(self, images=None, labels=None, eps: int = 0, steps: int = 1, alpha=None,
+               average: Optional[bool] = None) -> torch.Tensor:
+        """Adversarial images of the current weights: FGSM (steps = 1) or PGD within `eps` grey
+        levels (0..255) of ``images`` (as predict()'s; with no arguments the test split and its
+        labels), `steps` (1..100) steps of `alpha` grey levels (None: eps at one step, else
+        max(1, round(2.5 eps / steps))) up the plain NLL of ``labels``, from the images themselves
+        (no random start).  uint8 [N, 784] on the host.  ``average``: as evaluate()'s.  Only the
+        mlp model has an input-gradient kernel (csrc/kernels/mlp_attack.hip); nothing of the
+        training state is touched."""
+        if self.model != "mlp":
+            raise ValueError(f"the {self.model} model has no input-gradient kernel: attack() is "
+                             "built for --arch mlp only")
+        eps, steps, alpha = check_attack(eps, steps, alpha)
+        arena = self._eval_arena(average)
+        if images is None:
+            if labels is not None:
+                raise ValueError("labels without images")
+            if self.gpu is not None:
+                images, labels = self.gpu.test_images, self.gpu.test_labels
+            else:
+                images, labels = self.test_split.images, self.test_split.labels
+        else:
+            images = image_rows(images)
+            if labels is None:
+                raise ValueError("attack() needs the labels whose loss it climbs")
+            labels = label_vector(labels, images.shape[0])
+        if self.gpu is not None:
+            ws = None if arena is self.arena else self.gpu.weight_set(arena)
+            out = self.gpu.attack(images, labels, eps, steps, alpha, ws)
+            if self.sync_fn is not None:
+                self.sync_fn("attack")
+            return out.cpu()
+        return torch.cat([attack_step_cpu(self.model, arena, images[start:start + size],
+                                          labels[start:start + size], eps, steps, alpha)
+                          for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)])
 
     def _predict_tta_cpu(self, arena, images, labels, views: int):
         """The CPU path's predict() with `views` > 1 test-time views: per batch of rows, every

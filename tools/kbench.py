@@ -1,6 +1,7 @@
 """Per-kernel timing of the CNN step kernels at several batch sizes (CUDA events);
 `kbench.py mlp [B ...]`: the MLP's two kernels and its step; `kbench.py mlp2 [B ...]`: the
-two-hidden-layer MLP's hidden kernels (mlp_hid_fwd at both workgroup splits) and its step."""
+two-hidden-layer MLP's hidden kernels (mlp_hid_fwd at both workgroup splits) and its step;
+`kbench.py mlp_attack [B ...]`: mlp_attack at both workgroup splits beside its mlp_fwd."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -90,7 +91,31 @@ def mlp2(sizes):
               f" | step={step:.1f}us -> {B / step:.2f}M img/s", flush=True)
 
 
+def mlp_attack(sizes):
+    """mlp_attack (csrc/kernels/mlp_attack.hip) with seven workgroups per m-tile and with one,
+    beside the mlp_fwd launch that feeds it, at each batch size."""
+    for B in sizes:
+        p = build_local_program("mlp", "fp32", "cuda", B, train, test, optimizer="sgd", lr=0.01,
+                                use_graphs=False)
+        st = p.gpu
+        C, P = st.C, st.P
+        x0 = train.images[:B].cuda()
+        y = train.labels[:B].to(torch.int32).cuda()
+        out = torch.empty_like(x0)
+        n = 128 * 784
+        fwd = lambda: st._fwd(x0, y, None, B, B, st.w1split)
+        S = fwd()
+        atk = lambda pb: C.mlp_attack(st.part, S, B, st.ylab, P["fc1.bias"], P["fc2.weight"],
+                                      P["fc2.bias"], st.w1split[:n], st.w1split[n:], x0, x0, out,
+                                      25, 6, None, pb)
+        t = [(timeit(fwd), timeit(lambda: atk(7)), timeit(lambda: atk(1))) for _ in range(3)]
+        print(f"mlp_attack B={B:5d} S={S} mlp_fwd|px_blocks=7|px_blocks=1 x3: " +
+              " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}" for a, b, c in t), flush=True)
+
+
 def main():
+  if sys.argv[1:2] == ["mlp_attack"]:
+      return mlp_attack([int(b) for b in (sys.argv[2:] or ["32", "256", "2048"])])
   if sys.argv[1:2] == ["mlp"]:
       return mlp([int(b) for b in (sys.argv[2:] or ["32", "256", "4096"])])
   if sys.argv[1:2] == ["mlp2"]:

@@ -183,7 +183,36 @@ def mlp_hid_fwd(pitch=136):
     print("mlp_hid_fwd pitch %d dwords: b64 writes %.2f | b128 fragment reads %.2f" % (pitch, wt / wi, rt / ri))
 
 
+def mlp_attack(pitch=224, consecutive=True):
+    """mlp_attack's W1 tile ([128 units][112 pixels] bf16 per plane, `pitch` bytes per unit): the
+    staging ds_write_b128 (thread t, piece u: row-major 16-B piece t + 256 u of the 14 per row) and
+    the ds_read_b64_tr_b16 A fragments (lane (g, 4 q + pq): unit 32 ks + 4 g + q with the
+    kernel's k assignment, 32 ks + 8 g + q with the usual one; pixels 16 t + 4 pq .. + 3)."""
+    wt = wi = rt = ri = 0
+    for wave in range(4):
+        for u in range(7):         # one plane
+            addrs = []
+            for l in range(64):
+                n, c = divmod(64 * wave + l + 256 * u, 14)
+                addrs.append(n * pitch + 16 * c)
+            cy, idl = cycles_w128(addrs); wt += cy; wi += idl
+    for ks in range(4):
+        for t in range(7):
+            for half in range(2):
+                addrs = []
+                for l in range(64):
+                    g, q, pq = l >> 4, (l >> 2) & 3, l & 3
+                    row = 32 * ks + (4 * g + q + 16 * half if consecutive else 8 * g + q + 4 * half)
+                    addrs.append(row * pitch + 32 * t + 8 * pq)
+                cy, idl = cycles(addrs, 'tr16'); rt += cy; ri += idl
+    print("mlp_attack pitch %d, %s rows: b128 writes %.2f | tr16 fragment reads %.2f" %
+          (pitch, "4 g + q" if consecutive else "8 g + q", wt / wi, rt / ri))
+
+
 if __name__ == "__main__":
+    for pitch in (224, 240, 256, 272, 288):
+        mlp_attack(pitch, True)
+        mlp_attack(pitch, False)
     for pitch in (128, 132, 136, 144):
         mlp_hid_fwd(pitch)
     for pitch in (128, 136, 144):

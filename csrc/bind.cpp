@@ -1403,6 +1403,49 @@ void mlp_attack(at::Tensor part, int64_t splitk, int64_t B, at::Tensor ylab, at:
                     (int)px_blocks, cur_stream(part));
 }
 
+// ------------------------------------------------------------------ MLP int8 evaluation (mlp_i8.hip)
+void mlp_quant_w1(at::Tensor w1, at::Tensor b1, at::Tensor q1, at::Tensor s1, at::Tensor r1,
+                  at::Tensor c1, at::Tensor d1) {
+  c10::DeviceGuard g(w1.device());
+  need(w1, at::kFloat, "w1");
+  need(b1, at::kFloat, "b1");
+  TORCH_CHECK(w1.numel() == (int64_t)CNN_HID * MLP_IN && b1.numel() == CNN_HID,
+              "fc1 weight [128, 784] and bias [128]");
+  need_aligned(w1.data_ptr(), 16, "w1");
+  need(q1, at::kChar, "q1");
+  TORCH_CHECK(q1.numel() == (int64_t)CNN_HID * MLP_I8_KPAD, "q1 [128, 832]");
+  need_aligned(q1.data_ptr(), 4, "q1");
+  need(r1, at::kInt, "r1");
+  for (const at::Tensor* t : {&s1, &c1, &d1}) need(*t, at::kFloat, "s1 / c1 / d1");
+  TORCH_CHECK(s1.numel() == CNN_HID && r1.numel() == CNN_HID && c1.numel() == CNN_HID &&
+                  d1.numel() == CNN_HID, "s1 / r1 / c1 / d1 [128]");
+  launch_mlp_quant_w1(w1.data_ptr<float>(), b1.data_ptr<float>(), q1.data_ptr<int8_t>(),
+                      s1.data_ptr<float>(), r1.data_ptr<int32_t>(), c1.data_ptr<float>(),
+                      d1.data_ptr<float>(), cur_stream(w1));
+}
+
+void mlp_fwd_i8(at::Tensor images, at::Tensor labels, int64_t B, at::Tensor q1, at::Tensor c1,
+                at::Tensor part, at::Tensor ylab, int64_t splitk) {
+  c10::DeviceGuard g(images.device());
+  need(images, at::kByte, "images");
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == MLP_IN, "images [N, 784]");
+  TORCH_CHECK(B >= 1 && B <= (1 << 24) && images.size(0) >= B, "batch size");
+  need_aligned(images.data_ptr(), 16, "images");
+  need(labels, at::kInt, "labels");
+  TORCH_CHECK(labels.numel() >= B, "labels [>= B]");
+  TORCH_CHECK(splitk == 1 || splitk == 13, "splitk must be 1 or 13, got ", splitk);
+  need(q1, at::kChar, "q1");
+  TORCH_CHECK(q1.numel() == (int64_t)CNN_HID * MLP_I8_KPAD, "q1 [128, 832]");
+  need_aligned(q1.data_ptr(), 16, "q1");
+  need(c1, at::kFloat, "c1");
+  TORCH_CHECK(c1.numel() == CNN_HID, "c1 [128]");
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need_min(ylab, at::kInt, B, "ylab");
+  launch_mlp_fwd_i8(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), images.size(0), (int)B,
+                    q1.data_ptr<int8_t>(), c1.data_ptr<float>(), part.data_ptr<float>(),
+                    ylab.data_ptr<int32_t>(), (int)splitk, cur_stream(images));
+}
+
 // ------------------------------------------------------------------ MLP, two hidden layers (mlp_hid.hip)
 static void check_mlp_hid_w(const at::Tensor& w2) {
   need(w2, at::kFloat, "w2");
@@ -1608,6 +1651,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("whi"), py::arg("wlo"), py::arg("x0"),
         py::arg("x"), py::arg("out"), py::arg("eps"), py::arg("alpha"), py::arg("grad") = py::none(),
         py::arg("px_blocks") = 0);
+  m.attr("MLP_I8_KPAD") = MLP_I8_KPAD;
+  m.def("mlp_quant_w1", &mlp_quant_w1, py::arg("w1"), py::arg("b1"), py::arg("q1"), py::arg("s1"),
+        py::arg("r1"), py::arg("c1"), py::arg("d1"));
+  m.def("mlp_fwd_i8", &mlp_fwd_i8, py::arg("images"), py::arg("labels"), py::arg("B"), py::arg("q1"),
+        py::arg("c1"), py::arg("part"), py::arg("ylab"), py::arg("splitk"));
   m.def("mlp_hid_fwd", &mlp_hid_fwd, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("b1"),
         py::arg("w2"), py::arg("h1"), py::arg("pre2"), py::arg("ngroups") = 2);
   m.def("mlp_hid_bwd", &mlp_hid_bwd, py::arg("dh2"), py::arg("h1"), py::arg("w2"), py::arg("B"),

@@ -409,6 +409,23 @@ void launch_mlp_attack(const float* part, int splitk, int B, const int32_t* ylab
                        const uint8_t* x0, const uint8_t* x, uint8_t* out, float* grad, int eps,
                        int alpha, int px_blocks, hipStream_t st);
 
+// ---------------------------------------------------------------- MLP int8 evaluation (mlp_i8.hip)
+// fc1 of both MLPs with per-row int8 weights on the integer MFMA (docs/kernels.md "int8
+// evaluation"); the image byte is the other operand, exact as u8 - 128.
+constexpr int MLP_I8_KPAD = 832;     // q1's row pitch: 13 k-steps of 64, columns >= 784 zero
+// Once per weight set, from the fp32 fc1.weight [128][784] (16-B aligned) and fc1.bias [128]:
+// q1 int8 [128][832] (4-B aligned), s1 [128] the row scales, r1 int32 [128] the row sums of q1,
+// c1 = alpha s1 and d1 = b1 + (s1 r1) gamma, each fp32 operation rounded on its own.
+void launch_mlp_quant_w1(const float* w1, const float* b1, int8_t* q1, float* s1, int32_t* r1,
+                         float* c1, float* d1, hipStream_t st);
+// part [splitk][B][128] = c1[n] (float)(this split's share of sum_k q1[n][k] (u8[b][k] - 128)),
+// launch_mlp_fwd's layout without bias (the consumers take d1 as fc1's bias), and ylab[B], of
+// rows 0 .. B - 1 of images [nrow >= B][784] (16-B aligned, as q1); splitk in {1, 13}.  No load
+// leaves the nrow rows.
+void launch_mlp_fwd_i8(const uint8_t* images, const int32_t* labels, int64_t nrow, int B,
+                       const int8_t* q1, const float* c1, float* part, int32_t* ylab, int splitk,
+                       hipStream_t st);
+
 // ---------------------------------------------------------------- MLP, two hidden layers (mlp_hid.hip)
 // The 128 -> 128 layer of --arch mlp2 (784 -> 128 -> ReLU -> 128 -> ReLU -> 10) on the fp32
 // MFMA, between launch_mlp_fwd / launch_mlp_bwd and the head (docs/kernels.md "MLP, two hidden

@@ -28,6 +28,7 @@ from .parallel.comm import LocalComm
 from .parallel.dist import pick_device
 from .parallel.reducer import GradReducer
 from .runtime.arena import FlatArena
+from .runtime.cpu_step import check_quantize
 from .runtime.program import Prediction, TrainProgram
 from .utils.checkpoint import load_checkpoint
 
@@ -39,13 +40,15 @@ class Predictor:
         self.program = program
         self.arch, self.dtype, self.device = program.model, program.dtype, program.device
 
-    def predict(self, images, labels=None) -> Prediction:
+    def predict(self, images, labels=None, quantize: Optional[str] = None) -> Prediction:
         """images: uint8 [N, 28, 28] or [N, 784] (raw pixels; normalisation happens inside), as
         a torch tensor or a NumPy array, N >= 1; labels: N class indices, optional.  Returns
         log_probs fp32 [N, 10], pred int64 [N] and confusion int64 [10, 10] (None without
         labels), on the host.  With test-time augmentation on (``load_predictor(tta=V,
-        augment=spec)``) log_probs is the log of the mean probability over the V views."""
-        return self.program.predict(images, labels)
+        augment=spec)``) log_probs is the log of the mean probability over the V views.
+        ``quantize="int8"`` (``mlp`` / ``mlp2``; None: ``load_predictor``'s): the first layer
+        runs on per-row int8 weights, as ``--quantize int8``."""
+        return self.program.predict(images, labels, quantize=quantize)
 
     def attack(self, images, labels, eps: int, steps: int = 1, alpha=None) -> torch.Tensor:
         """Adversarial images (``--arch mlp`` only): FGSM (steps = 1) or PGD without random start
@@ -57,7 +60,8 @@ class Predictor:
 
 def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
                    dtype: str = "auto", ema: bool = False, tta: int = 1,
-                   augment: Optional[AugmentSpec] = None) -> Predictor:
+                   augment: Optional[AugmentSpec] = None,
+                   quantize: Optional[str] = None) -> Predictor:
     """Build ``arch`` ("linear", "cnn", "mlp" or "mlp2") on ``device`` ("auto", "cuda" or "cpu") and load the
     checkpoint's weights -- with ``ema=True`` its averaged weights (``ema_state_dict``, written
     by runs with ``--ema-decay``; a checkpoint without them raises KeyError).  A checkpoint of
@@ -66,8 +70,13 @@ def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
     ``tta`` (1..32) and ``augment`` (an ``AugmentSpec``): test-time augmentation, as ``--tta V``
     with the run's ``--aug-*`` flags -- ``predict`` combines ``tta`` views per image, view 0 the
     image itself and the others drawn with ``augment``'s ranges and seed for the row's position
-    in ``images``.  ``tta > 1`` without an enabled spec raises ValueError."""
+    in ``images``.  ``tta > 1`` without an enabled spec raises ValueError.
+
+    ``quantize`` (None or "int8"): ``predict``'s default for its keyword of the same name --
+    "int8" classifies with fc1's weights quantised per row to int8 (``mlp`` and ``mlp2`` only;
+    any other value or arch raises a ValueError saying there is no int8 kernel)."""
     tta = check_tta(tta, augment)
+    quantize = check_quantize(arch, quantize)
     dev = pick_device(0, device)
     spec = get_spec(arch)
     arena = FlatArena(spec, dev)
@@ -84,20 +93,28 @@ def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
     empty = MnistSplit(torch.empty(0, IMAGE_PIXELS, dtype=torch.uint8),
                        torch.empty(0, dtype=torch.int64), "none")
     program = TrainProgram(arch, resolve_dtype(dtype, arch, dev), arena, opt, reducer, empty, empty,
-                           batch_size=1, use_graphs=False, tta=tta, tta_augment=augment)
+                           batch_size=1, use_graphs=False, tta=tta, tta_augment=augment,
+                           quantize=quantize)
     if dev.type == "cuda":
         program.sync_fn = lambda what: torch.cuda.synchronize(dev)
     return Predictor(program)
 
 
 def save_predictions(path: str, prediction: Prediction, labels,
-                     adversarial: Optional[Prediction] = None) -> None:
+                     adversarial: Optional[Prediction] = None,
+                     int8: Optional[Prediction] = None) -> None:
     """Write ``path`` (a NumPy .npz with log_probs, pred, labels, confusion) atomically:
     temporary file in the same directory, then ``os.replace``, as checkpoints are.  With
     ``adversarial`` (the prediction on the attacked images, ``--attack-eps``) the file also
-    holds adv_log_probs, adv_pred and adv_confusion."""
+    holds adv_log_probs, adv_pred and adv_confusion; with ``int8`` (the prediction under the
+    int8 weight set, ``--quantize int8``) int8_log_probs, int8_pred and int8_confusion."""
     import os
     import tempfile
+    more = {}
+    for prefix, p in (("adv", adversarial), ("int8", int8)):
+        if p is not None:
+            more.update({prefix + "_log_probs": p.log_probs.numpy(), prefix + "_pred": p.pred.numpy(),
+                         prefix + "_confusion": p.confusion.numpy()})
     d = os.path.dirname(path) or "."
     os.makedirs(d, exist_ok=True)
     fd, tmp = tempfile.mkstemp(prefix=".tmp_pred_", dir=d)
@@ -105,11 +122,7 @@ def save_predictions(path: str, prediction: Prediction, labels,
         with os.fdopen(fd, "wb") as f:
             np.savez(f, log_probs=prediction.log_probs.numpy(), pred=prediction.pred.numpy(),
                      labels=torch.as_tensor(labels).to(torch.int64).cpu().numpy(),
-                     confusion=prediction.confusion.numpy(),
-                     **({} if adversarial is None else {
-                         "adv_log_probs": adversarial.log_probs.numpy(),
-                         "adv_pred": adversarial.pred.numpy(),
-                         "adv_confusion": adversarial.confusion.numpy()}))
+                     confusion=prediction.confusion.numpy(), **more)
         os.replace(tmp, path)
     except BaseException:
         if os.path.exists(tmp):

@@ -8,6 +8,7 @@ the gradients land in kernel layout directly in the gradient arena.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -94,7 +95,11 @@ def predict_step_cpu(model: str, arena, images_u8, labels=None):
     confusion[y][pred] counts the rows of class y predicted as pred)."""
     x = normalize_reference(images_u8)
     views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}
-    logits = functional_forward(model, views, x)
+    return _prediction(functional_forward(model, views, x), labels)
+
+
+def _prediction(logits, labels):
+    """predict_step_cpu's triple from the logits."""
     log_probs = F.log_softmax(logits, dim=1)
     pred = logits.argmax(dim=1)
     confusion = None
@@ -103,6 +108,54 @@ def predict_step_cpu(model: str, arena, images_u8, labels=None):
         confusion = torch.bincount(labels.to(torch.int64) * ncls + pred,
                                    minlength=ncls * ncls).view(ncls, ncls)
     return log_probs, pred, confusion
+
+
+def check_quantize(model: str, quantize):
+    """`quantize` as None or "int8"; anything else, or a model other than the two MLPs (whose
+    fc1 takes the raw image bytes: csrc/kernels/mlp_i8.hip), is a ValueError."""
+    if quantize is None:
+        return None
+    if quantize != "int8" or model not in ("mlp", "mlp2"):
+        raise ValueError(f"no int8 kernel for quantize={quantize!r} on the {model} model: "
+                         "quantize=\"int8\" is built for --arch mlp and mlp2 only")
+    return quantize
+
+
+# the normalisation x = alpha u8 - beta as the fc1 kernels fold it, and gamma = 128 alpha - beta
+I8_ALPHA = np.float32(1.0 / (255.0 * 0.3081))
+I8_GAMMA = np.float32(128.0 / (255.0 * 0.3081) - 0.1307 / 0.3081)
+
+
+def quantize_fc1(arena) -> dict:
+    """Per-row int8 quantisation of `arena`'s fc1 (docs/kernels.md "int8 evaluation"; the CPU twin
+    and oracle of mlp_quant_w1, bit for bit: NumPy float32, every operation rounded on its own).
+    Per hidden unit n: s1 = max_k |W1[n][k]| / 127 (1 for an all-zero row), q1 = clamp(rint(W1 /
+    s1), -127, 127) with ties to even, r1 = sum_k q1, c1 = alpha s1, d1 = b1 + (s1 r1) gamma.
+    {"q1": int8 [128, 784], "s1", "c1", "d1": float32 [128], "r1": int32 [128]}, NumPy."""
+    w = arena.param("fc1.weight").detach().cpu().numpy().astype(np.float32).reshape(128, 784)
+    b = arena.param("fc1.bias").detach().cpu().numpy().astype(np.float32)
+    m = np.abs(w).max(axis=1)
+    s1 = np.where(m == 0, np.float32(1), m / np.float32(127)).astype(np.float32)
+    q1 = np.clip(np.rint(w / s1[:, None]), -127, 127).astype(np.int8)
+    r1 = q1.sum(axis=1, dtype=np.int32)
+    d1 = b + (s1 * r1.astype(np.float32)) * I8_GAMMA
+    return {"q1": q1, "s1": s1, "r1": r1, "c1": I8_ALPHA * s1, "d1": d1.astype(np.float32)}
+
+
+@torch.no_grad()
+def predict_step_cpu_int8(model: str, arena, q: dict, images_u8, labels=None):
+    """predict_step_cpu with fc1 quantised (`q`: quantize_fc1 of `arena`): pre = c1 I + d1 with
+    I = sum_k q1 (u8 - 128) an exact integer product, then the reference forward's remaining
+    layers in fp32."""
+    views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}
+    acc = (images_u8.reshape(-1, 784).to(torch.int32) - 128) @ torch.from_numpy(q["q1"]).to(torch.int32).t()
+    h = F.relu(torch.from_numpy(q["c1"]) * acc.to(torch.float32) + torch.from_numpy(q["d1"]))
+    if model == "mlp2":
+        h = F.relu(F.linear(h, views["fc2.weight"], views["fc2.bias"]))
+        logits = F.linear(h, views["fc3.weight"], views["fc3.bias"])
+    else:
+        logits = F.linear(h, views["fc2.weight"], views["fc2.bias"])
+    return _prediction(logits, labels)
 
 
 def check_attack(eps, steps, alpha):

@@ -72,7 +72,9 @@ class Mlp2Step(MlpStep):
         self._update_one_bucket()
 
     def _eval_forward(self, images, labels, b, ws):
-        ws = (self.P, self.w1split) if ws is None else ws
-        P = ws[0]
-        self._fwd2(images, labels, None, b, b, ws, None)
+        P, w1 = (self.P, self.w1split) if ws is None else ws
+        # (an int8 weight set: mlp_fwd_i8's partials, and d1 in fc1.bias's place)
+        part, s = self._eval_fc1(images, labels, b, w1)
+        self.C.mlp_hid_fwd(part, s, b, P["fc1.bias"], P["fc2.weight"], None, self.pre2,
+                           ngroups=hid_groups(b))
         return self.pre2, 1, P["fc2.bias"], P["fc3.weight"], P["fc3.bias"]

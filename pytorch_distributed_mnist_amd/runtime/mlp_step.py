@@ -10,9 +10,13 @@ The image operand of both GEMMs is exact in bf16; fc1's weight goes in as hi / l
 that the optimizer keeps current (``csrc/kernels/mlp.hip``, docs/kernels.md "MLP").
 
 Evaluation and prediction are GpuStepBase's (gpu_step.py): per chunk of EVAL_CHUNK images,
-_eval_forward below -- mlp_fwd -- then cnn_head or cnn_predict_head.
+_eval_forward below -- mlp_fwd -- then cnn_head or cnn_predict_head.  With an int8 weight set
+(weight_set_int8: predict(quantize="int8")) the chunk's fc1 is mlp_fwd_i8 on the integer MFMA
+instead (``csrc/kernels/mlp_i8.hip``, docs/kernels.md "int8 evaluation"); the head is the same.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 
@@ -30,6 +34,25 @@ def mlp_splitk(b: int) -> int:
         if mt * s <= 512:
             return s
     return 1
+
+
+def mlp_i8_splitk(b: int) -> int:
+    """Split-K of mlp_fwd_i8 for b rows: the 13 k-steps of 64 over 13 workgroups per 16-row
+    m-tile while that keeps the launch within two rounds of the 256 CUs (b <= 624), else 1."""
+    return 13 if -(-b // 16) * 13 <= 512 else 1
+
+
+# rows of mlp_fwd_i8's partials for any chunk of up to EVAL_CHUNK rows
+I8_PART_ROWS = max(mlp_i8_splitk(b) * b for b in range(1, EVAL_CHUNK + 1))
+
+
+class Int8Fc1(NamedTuple):
+    """fc1 of an int8 weight set, in the place of the hi / lo planes: q1 int8 [128 x 832] (rows
+    zero-padded), c1 fp32 [128] = alpha s1, and the partials buffer mlp_fwd_i8 writes (sized for
+    any chunk of up to EVAL_CHUNK rows; the training step's own is sized for its splits)."""
+    q1: torch.Tensor
+    c1: torch.Tensor
+    part: torch.Tensor
 
 
 class MlpStep(GpuStepBase):
@@ -69,6 +92,22 @@ class MlpStep(GpuStepBase):
         return ({n: arena.param(n) for n in self.names},
                 split_bf16(arena.param("fc1.weight"), torch.empty_like(self.w1split)))
 
+    @torch.no_grad()
+    def weight_set_int8(self, arena):
+        """The int8 weight set of `arena` (the training weights or the averaged ones), built by
+        one mlp_quant_w1 launch: (name views with fc1.bias replaced by d1, Int8Fc1).  Fresh
+        tensors, outside any capture; nothing of `arena` or of the training step is touched."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("weight_set_int8() allocates: call it outside a graph capture")
+        dev, f32 = self.device, torch.float32
+        q1 = torch.empty(128 * self.C.MLP_I8_KPAD, dtype=torch.int8, device=dev)
+        s1, c1, d1 = (torch.empty(128, dtype=f32, device=dev) for _ in range(3))
+        r1 = torch.empty(128, dtype=torch.int32, device=dev)
+        self.C.mlp_quant_w1(arena.param("fc1.weight"), arena.param("fc1.bias"), q1, s1, r1, c1, d1)
+        P = {n: arena.param(n) for n in self.names}
+        P["fc1.bias"] = d1
+        return P, Int8Fc1(q1, c1, torch.empty(I8_PART_ROWS * 128, dtype=f32, device=dev))
+
     def optimizer_segments(self):
         segs = []
         for p in self.arena.spec.params:
@@ -104,10 +143,19 @@ class MlpStep(GpuStepBase):
                   self.metrics.train_view(), spe=self.spe, ctr_advanced=True)
         self._update_one_bucket()
 
+    def _eval_fc1(self, images, labels, b, w1):
+        """fc1's partials and ylab of b <= EVAL_CHUNK rows for evaluation: (part, splitk); w1 is
+        the hi / lo planes, or the Int8Fc1 of an int8 weight set."""
+        if isinstance(w1, Int8Fc1):
+            s = mlp_i8_splitk(b)
+            self.C.mlp_fwd_i8(images, labels, b, w1.q1, w1.c1, w1.part, self.ylab, s)
+            return w1.part, s
+        return self.part, self._fwd(images, labels, None, b, b, w1)
+
     def _eval_forward(self, images, labels, b, ws):
-        P, w1split = (self.P, self.w1split) if ws is None else ws
-        se = self._fwd(images, labels, None, b, b, w1split)
-        return self.part, se, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"]
+        P, w1 = (self.P, self.w1split) if ws is None else ws
+        part, se = self._eval_fc1(images, labels, b, w1)
+        return part, se, P["fc1.bias"], P["fc2.weight"], P["fc2.bias"]
 
     @torch.no_grad()
     def attack(self, images_u8: torch.Tensor, labels, eps: int, steps: int, alpha: int, ws=None,

@@ -29,8 +29,9 @@ from ..data.sampler import batch_bounds
 from ..optim.ema import EmaSpec, WeightEma
 from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
-from .cpu_step import (attack_step_cpu, check_attack, eval_step_cpu, predict_step_cpu,
-                       train_step_cpu, tta_reduce_cpu)
+from .cpu_step import (attack_step_cpu, check_attack, check_quantize, eval_step_cpu,
+                       predict_step_cpu, predict_step_cpu_int8, quantize_fc1, train_step_cpu,
+                       tta_reduce_cpu)
 from .structure import StepStructure
 
 
@@ -57,8 +58,13 @@ class TrainProgram:
                  dropout: Optional[DropoutSpec] = None,
                  schedule: Optional[ScheduleSpec] = None, label_smoothing: float = 0.0,
                  ema: Optional[WeightEma] = None, mixup: Optional[MixupSpec] = None,
-                 tta: int = 1, tta_augment: Optional[AugmentSpec] = None):
+                 tta: int = 1, tta_augment: Optional[AugmentSpec] = None,
+                 quantize: Optional[str] = None):
         self.model = model
+        # predict()'s default for its `quantize` keyword (load_predictor(quantize="int8")): None
+        # or "int8", the MLPs' first layer on int8 weights.  evaluate() and training never
+        # quantise.
+        self.quantize = check_quantize(model, quantize)
         # test-time augmentation (--tta V): evaluate() and predict() classify every image
         # together with V - 1 distorted views of it and combine the V log-softmax rows into the
         # log of the mean probability (docs/kernels.md "Test-time augmentation").  The views'
@@ -369,15 +375,23 @@ class TrainProgram:
 
     @torch.no_grad()
     def predict(self, images=None, labels=None, average: Optional[bool] = None,
-                tta: Optional[int] = None) -> Prediction:
+                tta: Optional[int] = None, quantize: Optional[str] = None) -> Prediction:
         """Per-sample predictions of the current weights: for ``images`` (uint8 [N, 28, 28] or
         [N, 784], torch or NumPy, any N >= 1; ``labels`` optional), or with no arguments for the
         test split and its labels.  Runs evaluate()'s forward; the metric accumulators are not
         touched.  ``average``: as evaluate()'s.  ``tta``: the number of test-time views per
         image (None: the program's; 1: none); with more than one, log_probs is the log of the
-        views' mean probability, and view v of row r is drawn for r's position in ``images``."""
+        views' mean probability, and view v of row r is drawn for r's position in ``images``.
+        ``quantize``: None (the program's default, ``self.quantize``) or "int8" -- the mlp and
+        mlp2 models' first layer with per-row int8 weights and the exact pixels (u8 - 128) on the
+        integer matrix cores, everything behind it as it is (docs/kernels.md "int8 evaluation");
+        the weights quantised are the ones ``average`` picks.  Not combined with test-time
+        views; another value or model raises ValueError."""
         arena = self._eval_arena(average)
         views = self.tta if tta is None else check_tta(tta, self.tta_augment)
+        quantize = check_quantize(self.model, self.quantize if quantize is None else quantize)
+        if quantize is not None and views > 1:
+            raise ValueError("quantize=\"int8\" evaluates the image itself, not test-time views")
         if images is None:
             if labels is not None:
                 raise ValueError("labels without images")
@@ -390,7 +404,10 @@ class TrainProgram:
             if labels is not None:
                 labels = label_vector(labels, images.shape[0])
         if self.gpu is not None:
-            ws = None if arena is self.arena else self.gpu.weight_set(arena)
+            if quantize is not None:
+                ws = self.gpu.weight_set_int8(arena)
+            else:
+                ws = None if arena is self.arena else self.gpu.weight_set(arena)
             if views > 1:
                 logp, pred, conf = self.gpu.predict_tta(images, labels, ws, self.tta_augment,
                                                         views)
@@ -402,8 +419,12 @@ class TrainProgram:
                               None if conf is None else conf.cpu())
         if views > 1:
             return Prediction(*self._predict_tta_cpu(arena, images, labels, views))
-        outs = [predict_step_cpu(self.model, arena, images[start:start + size],
-                                 None if labels is None else labels[start:start + size])
+        step = predict_step_cpu
+        if quantize is not None:
+            q = quantize_fc1(arena)
+            step = lambda m, a, x, y: predict_step_cpu_int8(m, a, q, x, y)   # noqa: E731
+        outs = [step(self.model, arena, images[start:start + size],
+                     None if labels is None else labels[start:start + size])
                 for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)]
         return Prediction(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
                           None if labels is None else sum(o[2] for o in outs))

@@ -1,7 +1,8 @@
 """Per-kernel timing of the CNN step kernels at several batch sizes (CUDA events);
 `kbench.py mlp [B ...]`: the MLP's two kernels and its step; `kbench.py mlp2 [B ...]`: the
 two-hidden-layer MLP's hidden kernels (mlp_hid_fwd at both workgroup splits) and its step;
-`kbench.py mlp_attack [B ...]`: mlp_attack at both workgroup splits beside its mlp_fwd."""
+`kbench.py mlp_attack [B ...]`: mlp_attack at both workgroup splits beside its mlp_fwd;
+`kbench.py mlp_i8 [B ...]`: mlp_fwd_i8 at both splits beside mlp_fwd, and mlp_quant_w1."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -113,7 +114,35 @@ def mlp_attack(sizes):
               " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}" for a, b, c in t), flush=True)
 
 
+def mlp_i8(sizes):
+    """mlp_fwd_i8 at both splits beside mlp_fwd (at its own split) on the same rows, interleaved,
+    at each batch size, and the one-off mlp_quant_w1 (csrc/kernels/mlp_i8.hip)."""
+    from pytorch_distributed_mnist_amd.runtime.mlp_step import mlp_i8_splitk
+    p = build_local_program("mlp", "fp32", "cuda", 1, train, test, optimizer="sgd", lr=0.01,
+                            use_graphs=False)
+    st = p.gpu
+    _, w = st.weight_set_int8(p.arena)
+    q1, s1, c1, d1 = (torch.empty_like(t) for t in (w.q1, w.c1, w.c1, w.c1))
+    r1 = torch.empty(128, dtype=torch.int32, device="cuda")
+    qk = lambda: st.C.mlp_quant_w1(p.arena.param("fc1.weight"), p.arena.param("fc1.bias"), q1, s1,
+                                   r1, c1, d1)
+    print("mlp_quant_w1 x3: " + " ".join(f"{timeit(qk):.2f}" for _ in range(3)), flush=True)
+    n = 128 * 784
+    for B in sizes:
+        x = train.images[:B].cuda()
+        y = train.labels[:B].to(torch.int32).cuda()
+        part = torch.empty(25 * B * 128, device="cuda")
+        S = mlp_splitk(B)
+        f32 = lambda: st.C.mlp_fwd(x, y, None, B, B, st.w1split[:n], st.w1split[n:], part, st.ylab, S)
+        i8 = lambda s: st.C.mlp_fwd_i8(x, y, B, w.q1, w.c1, part, st.ylab, s)
+        t = [(timeit(f32), timeit(lambda: i8(13)), timeit(lambda: i8(1))) for _ in range(3)]
+        print(f"mlp_i8 B={B:5d} mlp_fwd S={S}|mlp_fwd_i8 S=13|S=1 (rule: {mlp_i8_splitk(B)}) x3: " +
+              " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}" for a, b, c in t), flush=True)
+
+
 def main():
+  if sys.argv[1:2] == ["mlp_i8"]:
+      return mlp_i8([int(b) for b in (sys.argv[2:] or ["32", "256", "624", "625", "2048"])])
   if sys.argv[1:2] == ["mlp_attack"]:
       return mlp_attack([int(b) for b in (sys.argv[2:] or ["32", "256", "2048"])])
   if sys.argv[1:2] == ["mlp"]:

@@ -1446,6 +1446,48 @@ void mlp_fwd_i8(at::Tensor images, at::Tensor labels, int64_t B, at::Tensor q1, 
                     ylab.data_ptr<int32_t>(), (int)splitk, cur_stream(images));
 }
 
+// ------------------------------------------------------------------ MLP MXFP4 evaluation (mlp_mx4.hip)
+static void check_mx4_set(const at::Tensor& codes, const at::Tensor& scales) {
+  need(codes, at::kByte, "codes");
+  TORCH_CHECK(codes.numel() == (int64_t)CNN_HID * MLP_MX4_KPAD / 2, "codes [128, 448]");
+  need_aligned(codes.data_ptr(), 16, "codes");
+  need(scales, at::kByte, "scales");
+  TORCH_CHECK(scales.numel() == (int64_t)CNN_HID * MLP_MX4_KPAD / 32, "scales [128, 28]");
+}
+
+void mlp_quant_mx4(at::Tensor w1, at::Tensor b1, at::Tensor codes, at::Tensor scales,
+                   at::Tensor d1) {
+  c10::DeviceGuard g(w1.device());
+  need(w1, at::kFloat, "w1");
+  need(b1, at::kFloat, "b1");
+  TORCH_CHECK(w1.numel() == (int64_t)CNN_HID * MLP_IN && b1.numel() == CNN_HID,
+              "fc1 weight [128, 784] and bias [128]");
+  need_aligned(w1.data_ptr(), 16, "w1");
+  check_mx4_set(codes, scales);
+  need(d1, at::kFloat, "d1");
+  TORCH_CHECK(d1.numel() == CNN_HID, "d1 [128]");
+  launch_mlp_quant_mx4(w1.data_ptr<float>(), b1.data_ptr<float>(), codes.data_ptr<uint8_t>(),
+                       scales.data_ptr<uint8_t>(), d1.data_ptr<float>(), cur_stream(w1));
+}
+
+void mlp_fwd_mx4(at::Tensor images, at::Tensor labels, int64_t B, at::Tensor codes,
+                 at::Tensor scales, at::Tensor part, at::Tensor ylab, int64_t splitk) {
+  c10::DeviceGuard g(images.device());
+  need(images, at::kByte, "images");
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == MLP_IN, "images [N, 784]");
+  TORCH_CHECK(B >= 1 && B <= (1 << 24) && images.size(0) >= B, "batch size");
+  need_aligned(images.data_ptr(), 16, "images");
+  need(labels, at::kInt, "labels");
+  TORCH_CHECK(labels.numel() >= B, "labels [>= B]");
+  TORCH_CHECK(splitk == 1 || splitk == 7, "splitk must be 1 or 7, got ", splitk);
+  check_mx4_set(codes, scales);
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need_min(ylab, at::kInt, B, "ylab");
+  launch_mlp_fwd_mx4(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), images.size(0), (int)B,
+                     codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>(), part.data_ptr<float>(),
+                     ylab.data_ptr<int32_t>(), (int)splitk, cur_stream(images));
+}
+
 // ------------------------------------------------------------------ MLP, two hidden layers (mlp_hid.hip)
 static void check_mlp_hid_w(const at::Tensor& w2) {
   need(w2, at::kFloat, "w2");
@@ -1656,6 +1698,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("r1"), py::arg("c1"), py::arg("d1"));
   m.def("mlp_fwd_i8", &mlp_fwd_i8, py::arg("images"), py::arg("labels"), py::arg("B"), py::arg("q1"),
         py::arg("c1"), py::arg("part"), py::arg("ylab"), py::arg("splitk"));
+  m.attr("MLP_MX4_KPAD") = MLP_MX4_KPAD;
+  m.def("mlp_quant_mx4", &mlp_quant_mx4, py::arg("w1"), py::arg("b1"), py::arg("codes"),
+        py::arg("scales"), py::arg("d1"));
+  m.def("mlp_fwd_mx4", &mlp_fwd_mx4, py::arg("images"), py::arg("labels"), py::arg("B"),
+        py::arg("codes"), py::arg("scales"), py::arg("part"), py::arg("ylab"), py::arg("splitk"));
   m.def("mlp_hid_fwd", &mlp_hid_fwd, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("b1"),
         py::arg("w2"), py::arg("h1"), py::arg("pre2"), py::arg("ngroups") = 2);
   m.def("mlp_hid_bwd", &mlp_hid_bwd, py::arg("dh2"), py::arg("h1"), py::arg("w2"), py::arg("B"),

@@ -426,6 +426,24 @@ void launch_mlp_fwd_i8(const uint8_t* images, const int32_t* labels, int64_t nro
                        const int8_t* q1, const float* c1, float* part, int32_t* ylab, int splitk,
                        hipStream_t st);
 
+// ---------------------------------------------------------------- MLP MXFP4 evaluation (mlp_mx4.hip)
+// fc1 of both MLPs with OCP MXFP4 weights (E2M1 codes, one E8M0 scale per 32 consecutive k) on
+// the block-scaled MFMA (docs/kernels.md "MXFP4 evaluation"); the image byte is the other
+// operand, exact as two E4M3 nibbles.
+constexpr int MLP_MX4_KPAD = 896;    // a row's columns: 7 k-steps of 128 = 28 blocks, >= 784 zero
+// Once per weight set, from the fp32 fc1.weight [128][784] (16-B aligned) and fc1.bias [128]:
+// codes uint8 [128][448] (two per byte, even k low; 16-B aligned), scales uint8 [128][28] and
+// d1 = b1 - beta R, R the dequantised row sum added block by block, each operation rounded on its
+// own.
+void launch_mlp_quant_mx4(const float* w1, const float* b1, uint8_t* codes, uint8_t* scales,
+                          float* d1, hipStream_t st);
+// part [splitk][B][128] = alpha (this split's share of sum_k Wq[n][k] u8[b][k]), launch_mlp_fwd's
+// layout without bias (the consumers take d1 as fc1's bias), and ylab[B], of rows 0 .. B - 1 of
+// images [nrow >= B][784] (16-B aligned, as codes); splitk in {1, 7}.  No load leaves the nrow rows.
+void launch_mlp_fwd_mx4(const uint8_t* images, const int32_t* labels, int64_t nrow, int B,
+                        const uint8_t* codes, const uint8_t* scales, float* part, int32_t* ylab,
+                        int splitk, hipStream_t st);
+
 // ---------------------------------------------------------------- MLP, two hidden layers (mlp_hid.hip)
 // The 128 -> 128 layer of --arch mlp2 (784 -> 128 -> ReLU -> 128 -> ReLU -> 10) on the fp32
 // MFMA, between launch_mlp_fwd / launch_mlp_bwd and the head (docs/kernels.md "MLP, two hidden

@@ -289,24 +289,26 @@ def run(args):
                 out('adversarial (eps {}/255, {} steps, alpha {}/255) loss: {}, acc: {}.'.format(
                     eps, steps, alpha, Average.from_sums(float(nll), len(y)),
                     Accuracy.from_counts(int(adv.pred.eq(y).sum()), len(y))))
-            int8 = None
+            quant = {}
             if getattr(args, "quantize", None):
-                # int8 evaluation (--quantize int8, --arch mlp / mlp2): every rank classifies the
-                # whole test split under the int8 weight set, as it evaluates it
+                # quantised evaluation (--quantize int8 / mxfp4, --arch mlp / mlp2): every rank
+                # classifies the whole test split under the quantised weight set, as it evaluates it
                 from .utils.metrics import Accuracy, Average
                 y = test_split.labels.to(torch.int64)
-                int8 = program.predict(quantize=args.quantize)
-                nll = -int8.log_probs.gather(1, y[:, None]).to(torch.float64).sum()
-                out('int8 (fc1: per-row weights, exact pixels) loss: {}, acc: {}.'.format(
+                q = quant[args.quantize] = program.predict(quantize=args.quantize)
+                nll = -q.log_probs.gather(1, y[:, None]).to(torch.float64).sum()
+                out('{} loss: {}, acc: {}.'.format(
+                    {"int8": "int8 (fc1: per-row weights, exact pixels)",
+                     "mxfp4": "mxfp4 (fc1: 32-weight blocks, exact pixels)"}[args.quantize],
                     Average.from_sums(float(nll), len(y)),
-                    Accuracy.from_counts(int(int8.pred.eq(y).sum()), len(y))))
+                    Accuracy.from_counts(int(q.pred.eq(y).sum()), len(y))))
             if predict_out:
                 # every rank runs the (unsharded) pass, as it runs the evaluation; rank 0 writes
                 # the file and prints the per-class lines
                 from .predict import class_lines, save_predictions
                 pred = program.predict()
                 if rank == 0:
-                    save_predictions(predict_out, pred, test_split.labels, adv, int8)
+                    save_predictions(predict_out, pred, test_split.labels, adv, **quant)
                     for line in class_lines(pred.confusion):
                         out(line)
             return

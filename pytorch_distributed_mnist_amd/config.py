@@ -15,8 +15,8 @@ dropout on the CNN's hidden layer, ``--dropout`` / ``--dropout-seed``, the per-s
 ``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
 ``--label-smoothing``, mixup, ``--mixup`` / ``--mixup-seed``, the exponential moving average of the weights, ``--ema-decay`` /
 ``--ema-warmup``, test-time augmentation, ``--tta``, adversarial evaluation of ``--arch mlp``,
-``--attack-eps`` / ``--attack-steps`` / ``--attack-alpha``, and int8 evaluation of ``--arch mlp``
-/ ``mlp2``, ``--quantize``.
+``--attack-eps`` / ``--attack-steps`` / ``--attack-alpha``, and int8 / MXFP4 evaluation of
+``--arch mlp`` / ``mlp2``, ``--quantize``.
 """
 from __future__ import annotations
 
@@ -242,13 +242,15 @@ def build_parser() -> argparse.ArgumentParser:
                    default=argparse.SUPPRESS,
                    help='with --attack-eps: the step in grey levels (1..255; default L at one '
                         'step, else max(1, round(2.5 L / K)))')
-    # int8 evaluation (csrc/kernels/mlp_i8.hip; no default, as above: absent = off)
-    g.add_argument('--quantize', metavar='T', choices=['int8'], default=argparse.SUPPRESS,
+    # quantised evaluation (csrc/kernels/mlp_i8.hip, mlp_mx4.hip; no default, as above: absent =
+    # off)
+    g.add_argument('--quantize', metavar='T', choices=['int8', 'mxfp4'], default=argparse.SUPPRESS,
                    help='--evaluate --arch mlp / mlp2: after the test line, classify the test '
-                        'split once more with fc1\'s weights quantised per row to T = int8 (the '
-                        'pixels are exact; the later layers stay fp32) and print the loss and '
-                        'accuracy; with --predict-out the file also holds int8_log_probs, '
-                        'int8_pred and int8_confusion')
+                        'split once more with fc1\'s weights quantised to T: int8 per row, or '
+                        'mxfp4 (OCP MXFP4: 4-bit E2M1 codes with a power-of-two scale per 32 '
+                        'weights); the pixels are exact and the later layers stay fp32. Prints '
+                        'the loss and accuracy; with --predict-out the file also holds '
+                        'T_log_probs, T_pred and T_confusion')
     parser.set_defaults(local_rank_given=False)
     return parser
 
@@ -300,13 +302,13 @@ def parse_args(argv=None):
             parser.error("argument --quantize: post-training quantisation is an evaluation of a "
                          "trained model (use it with --evaluate --resume)")
         if args.arch not in ("mlp", "mlp2"):
-            parser.error("argument --quantize: --arch {} has no int8 kernel (only --arch mlp and "
-                         "mlp2 have one)".format(args.arch))
+            parser.error("argument --quantize: --arch {} has no {} kernel (only --arch mlp and "
+                         "mlp2 have one)".format(args.arch, args.quantize))
         if getattr(args, "tta", 1) > 1:
-            parser.error("argument --quantize: the int8 pass classifies the image itself, not "
+            parser.error("argument --quantize: the quantised pass classifies the image itself, not "
                          "--tta views (drop one of the two)")
         if attack:
-            parser.error("argument --quantize: the int8 pass and --attack-eps are separate "
+            parser.error("argument --quantize: the quantised pass and --attack-eps are separate "
                          "evaluations (drop one of the two)")
     if hasattr(args, "ema_warmup") and not getattr(args, "ema_decay", 0.0):
         parser.error("argument --ema-warmup: there is no average to warm up (give --ema-decay D)")

@@ -111,10 +111,16 @@ def _prediction(logits, labels):
 
 
 def check_quantize(model: str, quantize):
-    """`quantize` as None or "int8"; anything else, or a model other than the two MLPs (whose
-    fc1 takes the raw image bytes: csrc/kernels/mlp_i8.hip), is a ValueError."""
+    """`quantize` as None, "int8" or "mxfp4"; anything else, or a model other than the two MLPs
+    (whose fc1 takes the raw image bytes: csrc/kernels/mlp_i8.hip, mlp_mx4.hip), is a
+    ValueError."""
     if quantize is None:
         return None
+    if quantize == "mxfp4":
+        if model not in ("mlp", "mlp2"):
+            raise ValueError(f"no mxfp4 kernel for quantize='mxfp4' on the {model} model: "
+                             "quantize=\"mxfp4\" is built for --arch mlp and mlp2 only")
+        return quantize
     if quantize != "int8" or model not in ("mlp", "mlp2"):
         raise ValueError(f"no int8 kernel for quantize={quantize!r} on the {model} model: "
                          "quantize=\"int8\" is built for --arch mlp and mlp2 only")
@@ -147,15 +153,67 @@ def predict_step_cpu_int8(model: str, arena, q: dict, images_u8, labels=None):
     """predict_step_cpu with fc1 quantised (`q`: quantize_fc1 of `arena`): pre = c1 I + d1 with
     I = sum_k q1 (u8 - 128) an exact integer product, then the reference forward's remaining
     layers in fp32."""
-    views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}
     acc = (images_u8.reshape(-1, 784).to(torch.int32) - 128) @ torch.from_numpy(q["q1"]).to(torch.int32).t()
-    h = F.relu(torch.from_numpy(q["c1"]) * acc.to(torch.float32) + torch.from_numpy(q["d1"]))
+    pre = torch.from_numpy(q["c1"]) * acc.to(torch.float32) + torch.from_numpy(q["d1"])
+    return _prediction(_behind_fc1(model, arena, pre), labels)
+
+
+def _behind_fc1(model: str, arena, pre):
+    """The logits of an MLP from fc1's pre-activations: the reference forward's remaining layers."""
+    views = {p.name: p.to_torch(arena.param(p.name)) for p in arena.spec.params}
+    h = F.relu(pre)
     if model == "mlp2":
         h = F.relu(F.linear(h, views["fc2.weight"], views["fc2.bias"]))
-        logits = F.linear(h, views["fc3.weight"], views["fc3.bias"])
-    else:
-        logits = F.linear(h, views["fc2.weight"], views["fc2.bias"])
-    return _prediction(logits, labels)
+        return F.linear(h, views["fc3.weight"], views["fc3.bias"])
+    return F.linear(h, views["fc2.weight"], views["fc2.bias"])
+
+
+MX4_BETA = np.float32(0.1307 / 0.3081)
+E2M1_GRID = np.array([0, 0.5, 1, 1.5, 2, 3, 4, 6], np.float32)
+
+
+def quantize_fc1_mxfp4(arena) -> dict:
+    """OCP MXFP4 quantisation of `arena`'s fc1 (docs/kernels.md "MXFP4 evaluation"; the CPU twin
+    and oracle of mlp_quant_mx4, bit for bit).  Each row, padded with zeros to 896 columns, is 28
+    blocks of 32 consecutive k; a block with m = max |w| > 0 has e8 = clamp(floor(log2 m) - 2 +
+    127, 0, 254), taken from m's exponent field, and X = 2^(e8 - 127); m = 0 has e8 = 127.  v = w
+    / X (exact) goes to the nearest of 0, .5, 1, 1.5, 2, 3, 4, 6, ties to the code with mantissa
+    bit 0, above 6 to 6; code = sign << 3 | magnitude code, no negative zero.  R = the block sums
+    of the dequantised weights (exact) added in block order in float32, d1 = b1 - beta R in two
+    roundings.  {"codes": uint8 [128, 448] (even k in the low nibble), "scales": uint8 [128, 28],
+    "wq": float32 [128, 784] the dequantised weights, "d1": float32 [128]}, NumPy."""
+    w = arena.param("fc1.weight").detach().cpu().numpy().astype(np.float32).reshape(128, 784)
+    b = arena.param("fc1.bias").detach().cpu().numpy().astype(np.float32)
+    blk = np.zeros((128, 896), np.float32)
+    blk[:, :784] = w
+    blk = blk.reshape(128, 28, 32)
+    m = np.ascontiguousarray(np.abs(blk).max(axis=2))
+    field = ((m.view(np.uint32) >> 23) & 0xff).astype(np.int32)
+    e8 = np.where(m == 0, 127, np.maximum(field - 2, 0)).astype(np.int32)
+    a = np.abs(np.ldexp(blk, (127 - e8)[:, :, None]))
+    mag = ((a > 0.25).astype(np.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) +
+           (a >= 3.5) + (a > 5)).astype(np.uint8)
+    neg = (blk < 0) & (mag != 0)
+    code = (mag | (neg.astype(np.uint8) << 3)).reshape(128, 896)
+    wq = np.ldexp(np.where(neg, -E2M1_GRID[mag], E2M1_GRID[mag]), (e8 - 127)[:, :, None])
+    wq = wq.astype(np.float32)
+    sums = wq.sum(axis=2, dtype=np.float32)          # exact: 32 values of 2 bits on one scale
+    r = sums[:, 0]
+    for k in range(1, 25):
+        r = r + sums[:, k]
+    t = MX4_BETA * r
+    return {"codes": code[:, 0::2] | (code[:, 1::2] << 4), "scales": e8.astype(np.uint8),
+            "wq": np.ascontiguousarray(wq.reshape(128, 896)[:, :784]), "d1": (b - t).astype(np.float32)}
+
+
+@torch.no_grad()
+def predict_step_cpu_mxfp4(model: str, arena, q: dict, images_u8, labels=None):
+    """predict_step_cpu with fc1 in MXFP4 (`q`: quantize_fc1_mxfp4 of `arena`): pre = alpha I + d1
+    with I = sum_k wq u8 computed in float64 and rounded once to float32, then the reference
+    forward's remaining layers in fp32."""
+    acc = images_u8.reshape(-1, 784).to(torch.float64) @ torch.from_numpy(q["wq"]).to(torch.float64).t()
+    pre = torch.from_numpy(np.asarray(I8_ALPHA)) * acc.to(torch.float32) + torch.from_numpy(q["d1"])
+    return _prediction(_behind_fc1(model, arena, pre), labels)
 
 
 def check_attack(eps, steps, alpha):

@@ -12,7 +12,9 @@ that the optimizer keeps current (``csrc/kernels/mlp.hip``, docs/kernels.md "MLP
 Evaluation and prediction are GpuStepBase's (gpu_step.py): per chunk of EVAL_CHUNK images,
 _eval_forward below -- mlp_fwd -- then cnn_head or cnn_predict_head.  With an int8 weight set
 (weight_set_int8: predict(quantize="int8")) the chunk's fc1 is mlp_fwd_i8 on the integer MFMA
-instead (``csrc/kernels/mlp_i8.hip``, docs/kernels.md "int8 evaluation"); the head is the same.
+instead (``csrc/kernels/mlp_i8.hip``, docs/kernels.md "int8 evaluation"), with an MXFP4 one
+(weight_set_mxfp4: predict(quantize="mxfp4")) mlp_fwd_mx4 on the block-scaled MFMA
+(``csrc/kernels/mlp_mx4.hip``, docs/kernels.md "MXFP4 evaluation"); the head is the same.
 """
 from __future__ import annotations
 
@@ -52,6 +54,25 @@ class Int8Fc1(NamedTuple):
     any chunk of up to EVAL_CHUNK rows; the training step's own is sized for its splits)."""
     q1: torch.Tensor
     c1: torch.Tensor
+    part: torch.Tensor
+
+
+def mlp_mx4_splitk(b: int) -> int:
+    """Split-K of mlp_fwd_mx4 for b rows: the 7 k-steps of 128 over 7 workgroups per 16-row
+    m-tile while that keeps the launch within two rounds of the 256 CUs (b <= 1168), else 1."""
+    return 7 if -(-b // 16) * 7 <= 512 else 1
+
+
+# rows of mlp_fwd_mx4's partials for any chunk of up to EVAL_CHUNK rows
+MX4_PART_ROWS = max(mlp_mx4_splitk(b) * b for b in range(1, EVAL_CHUNK + 1))
+
+
+class Mx4Fc1(NamedTuple):
+    """fc1 of an MXFP4 weight set, in the place of the hi / lo planes: codes uint8 [128 x 448]
+    (two E2M1 codes per byte, rows zero-padded to 896 columns), scales uint8 [128 x 28] (one E8M0
+    byte per 32 columns), and the partials buffer mlp_fwd_mx4 writes (sized as Int8Fc1's)."""
+    codes: torch.Tensor
+    scales: torch.Tensor
     part: torch.Tensor
 
 
@@ -108,6 +129,23 @@ class MlpStep(GpuStepBase):
         P["fc1.bias"] = d1
         return P, Int8Fc1(q1, c1, torch.empty(I8_PART_ROWS * 128, dtype=f32, device=dev))
 
+    @torch.no_grad()
+    def weight_set_mxfp4(self, arena):
+        """The MXFP4 weight set of `arena`, built by one mlp_quant_mx4 launch: (name views with
+        fc1.bias replaced by d1, Mx4Fc1).  As weight_set_int8: fresh tensors, outside any
+        capture, nothing of `arena` or of the training step is touched."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("weight_set_mxfp4() allocates: call it outside a graph capture")
+        dev, kpad = self.device, self.C.MLP_MX4_KPAD
+        codes = torch.empty(128 * kpad // 2, dtype=torch.uint8, device=dev)
+        scales = torch.empty(128 * kpad // 32, dtype=torch.uint8, device=dev)
+        d1 = torch.empty(128, dtype=torch.float32, device=dev)
+        self.C.mlp_quant_mx4(arena.param("fc1.weight"), arena.param("fc1.bias"), codes, scales, d1)
+        P = {n: arena.param(n) for n in self.names}
+        P["fc1.bias"] = d1
+        return P, Mx4Fc1(codes, scales,
+                         torch.empty(MX4_PART_ROWS * 128, dtype=torch.float32, device=dev))
+
     def optimizer_segments(self):
         segs = []
         for p in self.arena.spec.params:
@@ -145,7 +183,11 @@ class MlpStep(GpuStepBase):
 
     def _eval_fc1(self, images, labels, b, w1):
         """fc1's partials and ylab of b <= EVAL_CHUNK rows for evaluation: (part, splitk); w1 is
-        the hi / lo planes, or the Int8Fc1 of an int8 weight set."""
+        the hi / lo planes, or the Int8Fc1 / Mx4Fc1 of a quantised weight set."""
+        if isinstance(w1, Mx4Fc1):
+            s = mlp_mx4_splitk(b)
+            self.C.mlp_fwd_mx4(images, labels, b, w1.codes, w1.scales, w1.part, self.ylab, s)
+            return w1.part, s
         if isinstance(w1, Int8Fc1):
             s = mlp_i8_splitk(b)
             self.C.mlp_fwd_i8(images, labels, b, w1.q1, w1.c1, w1.part, self.ylab, s)

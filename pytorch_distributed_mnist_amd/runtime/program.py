@@ -30,8 +30,8 @@ from ..optim.ema import EmaSpec, WeightEma
 from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
 from .cpu_step import (attack_step_cpu, check_attack, check_quantize, eval_step_cpu,
-                       predict_step_cpu, predict_step_cpu_int8, quantize_fc1, train_step_cpu,
-                       tta_reduce_cpu)
+                       predict_step_cpu, predict_step_cpu_int8, predict_step_cpu_mxfp4,
+                       quantize_fc1, quantize_fc1_mxfp4, train_step_cpu, tta_reduce_cpu)
 from .structure import StepStructure
 
 
@@ -61,9 +61,9 @@ class TrainProgram:
                  tta: int = 1, tta_augment: Optional[AugmentSpec] = None,
                  quantize: Optional[str] = None):
         self.model = model
-        # predict()'s default for its `quantize` keyword (load_predictor(quantize="int8")): None
-        # or "int8", the MLPs' first layer on int8 weights.  evaluate() and training never
-        # quantise.
+        # predict()'s default for its `quantize` keyword (load_predictor(quantize="int8")): None,
+        # "int8" or "mxfp4", the MLPs' first layer on int8 or MXFP4 weights.  evaluate() and
+        # training never quantise.
         self.quantize = check_quantize(model, quantize)
         # test-time augmentation (--tta V): evaluate() and predict() classify every image
         # together with V - 1 distorted views of it and combine the V log-softmax rows into the
@@ -385,13 +385,15 @@ class TrainProgram:
         ``quantize``: None (the program's default, ``self.quantize``) or "int8" -- the mlp and
         mlp2 models' first layer with per-row int8 weights and the exact pixels (u8 - 128) on the
         integer matrix cores, everything behind it as it is (docs/kernels.md "int8 evaluation");
-        the weights quantised are the ones ``average`` picks.  Not combined with test-time
-        views; another value or model raises ValueError."""
+        or "mxfp4" -- that layer with OCP MXFP4 weights (E2M1 codes, a power-of-two scale per 32
+        weights) and the exact pixels on the block-scaled MFMA (docs/kernels.md "MXFP4
+        evaluation"); the weights quantised are the ones ``average`` picks.  Not combined with
+        test-time views; another value or model raises ValueError."""
         arena = self._eval_arena(average)
         views = self.tta if tta is None else check_tta(tta, self.tta_augment)
         quantize = check_quantize(self.model, self.quantize if quantize is None else quantize)
         if quantize is not None and views > 1:
-            raise ValueError("quantize=\"int8\" evaluates the image itself, not test-time views")
+            raise ValueError(f"quantize=\"{quantize}\" evaluates the image itself, not test-time views")
         if images is None:
             if labels is not None:
                 raise ValueError("labels without images")
@@ -404,7 +406,9 @@ class TrainProgram:
             if labels is not None:
                 labels = label_vector(labels, images.shape[0])
         if self.gpu is not None:
-            if quantize is not None:
+            if quantize == "mxfp4":
+                ws = self.gpu.weight_set_mxfp4(arena)
+            elif quantize is not None:
                 ws = self.gpu.weight_set_int8(arena)
             else:
                 ws = None if arena is self.arena else self.gpu.weight_set(arena)
@@ -421,8 +425,9 @@ class TrainProgram:
             return Prediction(*self._predict_tta_cpu(arena, images, labels, views))
         step = predict_step_cpu
         if quantize is not None:
-            q = quantize_fc1(arena)
-            step = lambda m, a, x, y: predict_step_cpu_int8(m, a, q, x, y)   # noqa: E731
+            q, qstep = ((quantize_fc1_mxfp4(arena), predict_step_cpu_mxfp4) if quantize == "mxfp4"
+                        else (quantize_fc1(arena), predict_step_cpu_int8))
+            step = lambda m, a, x, y: qstep(m, a, q, x, y)   # noqa: E731
         outs = [step(self.model, arena, images[start:start + size],
                      None if labels is None else labels[start:start + size])
                 for start, size in batch_bounds(images.shape[0], PREDICT_BATCH_CPU)]

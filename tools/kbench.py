@@ -2,7 +2,9 @@
 `kbench.py mlp [B ...]`: the MLP's two kernels and its step; `kbench.py mlp2 [B ...]`: the
 two-hidden-layer MLP's hidden kernels (mlp_hid_fwd at both workgroup splits) and its step;
 `kbench.py mlp_attack [B ...]`: mlp_attack at both workgroup splits beside its mlp_fwd;
-`kbench.py mlp_i8 [B ...]`: mlp_fwd_i8 at both splits beside mlp_fwd, and mlp_quant_w1."""
+`kbench.py mlp_i8 [B ...]`: mlp_fwd_i8 at both splits beside mlp_fwd, and mlp_quant_w1;
+`kbench.py mlp_mx4 [B ...]`: mlp_fwd_mx4 at both splits beside mlp_fwd_i8 and mlp_fwd, and
+mlp_quant_mx4."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -140,7 +142,38 @@ def mlp_i8(sizes):
               " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}" for a, b, c in t), flush=True)
 
 
+def mlp_mx4(sizes):
+    """mlp_fwd_mx4 at both splits beside mlp_fwd_i8 and mlp_fwd (each at its own rule's split) on
+    the same rows, interleaved, at each batch size, and the one-off mlp_quant_mx4
+    (csrc/kernels/mlp_mx4.hip)."""
+    from pytorch_distributed_mnist_amd.runtime.mlp_step import mlp_i8_splitk, mlp_mx4_splitk
+    p = build_local_program("mlp", "fp32", "cuda", 1, train, test, optimizer="sgd", lr=0.01,
+                            use_graphs=False)
+    st = p.gpu
+    _, w8 = st.weight_set_int8(p.arena)
+    _, w4 = st.weight_set_mxfp4(p.arena)
+    codes, scales, d1 = torch.empty_like(w4.codes), torch.empty_like(w4.scales), torch.empty_like(w8.c1)
+    qk = lambda: st.C.mlp_quant_mx4(p.arena.param("fc1.weight"), p.arena.param("fc1.bias"), codes,
+                                    scales, d1)
+    print("mlp_quant_mx4 x3: " + " ".join(f"{timeit(qk):.2f}" for _ in range(3)), flush=True)
+    n = 128 * 784
+    for B in sizes:
+        x = train.images[:B].cuda()
+        y = train.labels[:B].to(torch.int32).cuda()
+        part = torch.empty(25 * B * 128, device="cuda")
+        S, S8 = mlp_splitk(B), mlp_i8_splitk(B)
+        f32 = lambda: st.C.mlp_fwd(x, y, None, B, B, st.w1split[:n], st.w1split[n:], part, st.ylab, S)
+        i8 = lambda: st.C.mlp_fwd_i8(x, y, B, w8.q1, w8.c1, part, st.ylab, S8)
+        mx = lambda s: st.C.mlp_fwd_mx4(x, y, B, w4.codes, w4.scales, part, st.ylab, s)
+        t = [(timeit(f32), timeit(i8), timeit(lambda: mx(7)), timeit(lambda: mx(1))) for _ in range(3)]
+        print(f"mlp_mx4 B={B:5d} mlp_fwd S={S}|mlp_fwd_i8 S={S8}|mlp_fwd_mx4 S=7|S=1 "
+              f"(rule: {mlp_mx4_splitk(B)}) x3: " +
+              " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}|{d:.2f}" for a, b, c, d in t), flush=True)
+
+
 def main():
+  if sys.argv[1:2] == ["mlp_mx4"]:
+      return mlp_mx4([int(b) for b in (sys.argv[2:] or ["32", "256", "1168", "1169", "2048"])])
   if sys.argv[1:2] == ["mlp_i8"]:
       return mlp_i8([int(b) for b in (sys.argv[2:] or ["32", "256", "624", "625", "2048"])])
   if sys.argv[1:2] == ["mlp_attack"]:

@@ -1488,6 +1488,54 @@ void mlp_fwd_mx4(at::Tensor images, at::Tensor labels, int64_t B, at::Tensor cod
                      ylab.data_ptr<int32_t>(), (int)splitk, cur_stream(images));
 }
 
+// ------------------------------------------------------------------ MLP 2:4 sparse evaluation (mlp_sp24.hip)
+static void check_sp24_set(const at::Tensor& whi, const at::Tensor& wlo, const at::Tensor& index) {
+  need(whi, at::kBFloat16, "whi");
+  need(wlo, at::kBFloat16, "wlo");
+  TORCH_CHECK(whi.numel() == (int64_t)CNN_HID * MLP_SP24_KPAD / 2 && wlo.numel() == whi.numel(),
+              "compressed fc1 weight planes [128, 416]");
+  for (const void* q : {whi.data_ptr(), wlo.data_ptr()}) need_aligned(q, 16, "compressed plane");
+  need(index, at::kInt, "index");
+  TORCH_CHECK(index.numel() == (int64_t)CNN_HID * 28, "index [128, 7, 4]");
+}
+
+void mlp_prune_24(at::Tensor w1, at::Tensor b1, at::Tensor whi, at::Tensor wlo, at::Tensor index,
+                  at::Tensor d1) {
+  c10::DeviceGuard g(w1.device());
+  need(w1, at::kFloat, "w1");
+  need(b1, at::kFloat, "b1");
+  TORCH_CHECK(w1.numel() == (int64_t)CNN_HID * MLP_IN && b1.numel() == CNN_HID,
+              "fc1 weight [128, 784] and bias [128]");
+  need_aligned(w1.data_ptr(), 16, "w1");
+  check_sp24_set(whi, wlo, index);
+  need(d1, at::kFloat, "d1");
+  TORCH_CHECK(d1.numel() == CNN_HID, "d1 [128]");
+  launch_mlp_prune_24(w1.data_ptr<float>(), b1.data_ptr<float>(), ptr<__bf16>(whi), ptr<__bf16>(wlo),
+                      reinterpret_cast<uint32_t*>(index.data_ptr<int32_t>()), d1.data_ptr<float>(),
+                      cur_stream(w1));
+}
+
+void mlp_fwd_sp24(at::Tensor images, at::Tensor labels, int64_t B, at::Tensor whi, at::Tensor wlo,
+                  at::Tensor index, at::Tensor part, at::Tensor ylab, int64_t splitk) {
+  c10::DeviceGuard g(images.device());
+  need(images, at::kByte, "images");
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == MLP_IN, "images [N, 784]");
+  TORCH_CHECK(B >= 1 && B <= (1 << 24) && images.size(0) >= B, "batch size");
+  need_aligned(images.data_ptr(), 16, "images");
+  need(labels, at::kInt, "labels");
+  TORCH_CHECK(labels.numel() >= B, "labels [>= B]");
+  TORCH_CHECK(splitk == 1 || splitk == 13, "splitk must be 1 or 13, got ", splitk);
+  check_sp24_set(whi, wlo, index);
+  need_min(part, at::kFloat, splitk * B * CNN_HID, "part");
+  need_aligned(part.data_ptr(), 16, "part");
+  need_min(ylab, at::kInt, B, "ylab");
+  launch_mlp_fwd_sp24(images.data_ptr<uint8_t>(), labels.data_ptr<int32_t>(), images.size(0), (int)B,
+                      ptr<__bf16>(whi), ptr<__bf16>(wlo),
+                      reinterpret_cast<const uint32_t*>(index.data_ptr<int32_t>()),
+                      part.data_ptr<float>(), ylab.data_ptr<int32_t>(), (int)splitk,
+                      cur_stream(images));
+}
+
 // ------------------------------------------------------------------ MLP, two hidden layers (mlp_hid.hip)
 static void check_mlp_hid_w(const at::Tensor& w2) {
   need(w2, at::kFloat, "w2");
@@ -1703,6 +1751,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("scales"), py::arg("d1"));
   m.def("mlp_fwd_mx4", &mlp_fwd_mx4, py::arg("images"), py::arg("labels"), py::arg("B"),
         py::arg("codes"), py::arg("scales"), py::arg("part"), py::arg("ylab"), py::arg("splitk"));
+  m.attr("MLP_SP24_KPAD") = MLP_SP24_KPAD;
+  m.def("mlp_prune_24", &mlp_prune_24, py::arg("w1"), py::arg("b1"), py::arg("whi"), py::arg("wlo"),
+        py::arg("index"), py::arg("d1"));
+  m.def("mlp_fwd_sp24", &mlp_fwd_sp24, py::arg("images"), py::arg("labels"), py::arg("B"),
+        py::arg("whi"), py::arg("wlo"), py::arg("index"), py::arg("part"), py::arg("ylab"),
+        py::arg("splitk"));
   m.def("mlp_hid_fwd", &mlp_hid_fwd, py::arg("part"), py::arg("splitk"), py::arg("B"), py::arg("b1"),
         py::arg("w2"), py::arg("h1"), py::arg("pre2"), py::arg("ngroups") = 2);
   m.def("mlp_hid_bwd", &mlp_hid_bwd, py::arg("dh2"), py::arg("h1"), py::arg("w2"), py::arg("B"),

@@ -444,6 +444,27 @@ void launch_mlp_fwd_mx4(const uint8_t* images, const int32_t* labels, int64_t nr
                         const uint8_t* codes, const uint8_t* scales, float* part, int32_t* ylab,
                         int splitk, hipStream_t st);
 
+// ---------------------------------------------------------------- MLP 2:4 sparse evaluation (mlp_sp24.hip)
+// fc1 of both MLPs with 2 of every 4 consecutive weights of a row kept (the larger magnitudes,
+// ties to the lower column) on the structured-sparsity MFMA (docs/kernels.md "2:4 sparse
+// evaluation"); the weights are its compressed A operand, as two bf16 planes, the image byte the
+// dense B operand.
+constexpr int MLP_SP24_KPAD = 832;   // a row's dense columns: 13 k-steps of 64, >= 784 zero
+// Once per weight set, from the fp32 fc1.weight [128][784] (16-B aligned) and fc1.bias [128]:
+// the survivors' planes whi / wlo bf16 [128][416] (16-B aligned; hi = bf16(w), lo = bf16(w - hi)),
+// index uint32 [128][7][4] (word (kp, g): the 2-bit positions of the 8 survivors of columns
+// 64 (2 kp + h) + 16 g .. + 15 in bits 16 h .. 16 h + 15) and d1 = b1 - beta R, R the survivors'
+// fp32 row sum in a fixed order.
+void launch_mlp_prune_24(const float* w1, const float* b1, __bf16* whi, __bf16* wlo, uint32_t* index,
+                         float* d1, hipStream_t st);
+// part [splitk][B][128] = alpha (this split's share of sum_k Wp[n][k] u8[b][k]), launch_mlp_fwd's
+// layout without bias (the consumers take d1 as fc1's bias), and ylab[B], of rows 0 .. B - 1 of
+// images [nrow >= B][784] (16-B aligned, as part); splitk in {1, 13}.  No load leaves the nrow
+// rows.
+void launch_mlp_fwd_sp24(const uint8_t* images, const int32_t* labels, int64_t nrow, int B,
+                         const __bf16* whi, const __bf16* wlo, const uint32_t* index, float* part,
+                         int32_t* ylab, int splitk, hipStream_t st);
+
 // ---------------------------------------------------------------- MLP, two hidden layers (mlp_hid.hip)
 // The 128 -> 128 layer of --arch mlp2 (784 -> 128 -> ReLU -> 128 -> ReLU -> 10) on the fp32
 // MFMA, between launch_mlp_fwd / launch_mlp_bwd and the head (docs/kernels.md "MLP, two hidden

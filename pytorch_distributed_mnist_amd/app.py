@@ -291,15 +291,17 @@ def run(args):
                     Accuracy.from_counts(int(adv.pred.eq(y).sum()), len(y))))
             quant = {}
             if getattr(args, "quantize", None):
-                # quantised evaluation (--quantize int8 / mxfp4, --arch mlp / mlp2): every rank
-                # classifies the whole test split under the quantised weight set, as it evaluates it
+                # quantised evaluation (--quantize int8 / mxfp4 / sparse24, --arch mlp / mlp2): every
+                # rank classifies the whole test split under the quantised or pruned weight set, as
+                # it evaluates it
                 from .utils.metrics import Accuracy, Average
                 y = test_split.labels.to(torch.int64)
                 q = quant[args.quantize] = program.predict(quantize=args.quantize)
                 nll = -q.log_probs.gather(1, y[:, None]).to(torch.float64).sum()
                 out('{} loss: {}, acc: {}.'.format(
                     {"int8": "int8 (fc1: per-row weights, exact pixels)",
-                     "mxfp4": "mxfp4 (fc1: 32-weight blocks, exact pixels)"}[args.quantize],
+                     "mxfp4": "mxfp4 (fc1: 32-weight blocks, exact pixels)",
+                     "sparse24": "sparse24 (fc1: 2 of every 4 weights, exact pixels)"}[args.quantize],
                     Average.from_sums(float(nll), len(y)),
                     Accuracy.from_counts(int(q.pred.eq(y).sum()), len(y))))
             if predict_out:

@@ -15,8 +15,8 @@ dropout on the CNN's hidden layer, ``--dropout`` / ``--dropout-seed``, the per-s
 ``--lr-schedule`` / ``--lr-warmup`` / ``--lr-min``, label smoothing of the training loss,
 ``--label-smoothing``, mixup, ``--mixup`` / ``--mixup-seed``, the exponential moving average of the weights, ``--ema-decay`` /
 ``--ema-warmup``, test-time augmentation, ``--tta``, adversarial evaluation of ``--arch mlp``,
-``--attack-eps`` / ``--attack-steps`` / ``--attack-alpha``, and int8 / MXFP4 evaluation of
-``--arch mlp`` / ``mlp2``, ``--quantize``.
+``--attack-eps`` / ``--attack-steps`` / ``--attack-alpha``, and int8 / MXFP4 / 2:4 sparse
+evaluation of ``--arch mlp`` / ``mlp2``, ``--quantize``.
 """
 from __future__ import annotations
 
@@ -242,13 +242,16 @@ def build_parser() -> argparse.ArgumentParser:
                    default=argparse.SUPPRESS,
                    help='with --attack-eps: the step in grey levels (1..255; default L at one '
                         'step, else max(1, round(2.5 L / K)))')
-    # quantised evaluation (csrc/kernels/mlp_i8.hip, mlp_mx4.hip; no default, as above: absent =
-    # off)
-    g.add_argument('--quantize', metavar='T', choices=['int8', 'mxfp4'], default=argparse.SUPPRESS,
+    # quantised / pruned evaluation (csrc/kernels/mlp_i8.hip, mlp_mx4.hip, mlp_sp24.hip; no
+    # default, as above: absent = off)
+    g.add_argument('--quantize', metavar='T', choices=['int8', 'mxfp4', 'sparse24'],
+                   default=argparse.SUPPRESS,
                    help='--evaluate --arch mlp / mlp2: after the test line, classify the test '
-                        'split once more with fc1\'s weights quantised to T: int8 per row, or '
+                        'split once more with fc1\'s weights quantised to T: int8 per row, '
                         'mxfp4 (OCP MXFP4: 4-bit E2M1 codes with a power-of-two scale per 32 '
-                        'weights); the pixels are exact and the later layers stay fp32. Prints '
+                        'weights), or sparse24 (2:4 magnitude pruning: the two larger of every 4 '
+                        'consecutive weights of a row, at fp32 precision); the pixels are exact '
+                        'and the later layers stay fp32. Prints '
                         'the loss and accuracy; with --predict-out the file also holds '
                         'T_log_probs, T_pred and T_confusion')
     parser.set_defaults(local_rank_given=False)

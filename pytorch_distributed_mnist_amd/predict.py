@@ -46,8 +46,9 @@ class Predictor:
         log_probs fp32 [N, 10], pred int64 [N] and confusion int64 [10, 10] (None without
         labels), on the host.  With test-time augmentation on (``load_predictor(tta=V,
         augment=spec)``) log_probs is the log of the mean probability over the V views.
-        ``quantize="int8"`` or ``"mxfp4"`` (``mlp`` / ``mlp2``; None: ``load_predictor``'s): the
-        first layer runs on per-row int8 weights or on OCP MXFP4 weights, as ``--quantize``."""
+        ``quantize="int8"``, ``"mxfp4"`` or ``"sparse24"`` (``mlp`` / ``mlp2``; None:
+        ``load_predictor``'s): the first layer runs on per-row int8 weights, on OCP MXFP4 weights
+        or on 2:4-pruned weights, as ``--quantize``."""
         return self.program.predict(images, labels, quantize=quantize)
 
     def attack(self, images, labels, eps: int, steps: int = 1, alpha=None) -> torch.Tensor:
@@ -72,10 +73,11 @@ def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
     image itself and the others drawn with ``augment``'s ranges and seed for the row's position
     in ``images``.  ``tta > 1`` without an enabled spec raises ValueError.
 
-    ``quantize`` (None, "int8" or "mxfp4"): ``predict``'s default for its keyword of the same
-    name -- "int8" classifies with fc1's weights quantised per row to int8, "mxfp4" with them in
-    OCP MXFP4 blocks of 32 (``mlp`` and ``mlp2`` only; any other value or arch raises a
-    ValueError saying there is no int8 kernel, or no mxfp4 kernel for "mxfp4")."""
+    ``quantize`` (None, "int8", "mxfp4" or "sparse24"): ``predict``'s default for its keyword of
+    the same name -- "int8" classifies with fc1's weights quantised per row to int8, "mxfp4" with
+    them in OCP MXFP4 blocks of 32, "sparse24" with the two larger of every 4 consecutive weights
+    of a row kept (``mlp`` and ``mlp2`` only; any other value or arch raises a ValueError saying
+    there is no int8 kernel, or no mxfp4 / sparse24 kernel for those two values)."""
     tta = check_tta(tta, augment)
     quantize = check_quantize(arch, quantize)
     dev = pick_device(0, device)
@@ -104,17 +106,21 @@ def load_predictor(checkpoint_path: str, arch: str, device: str = "auto",
 def save_predictions(path: str, prediction: Prediction, labels,
                      adversarial: Optional[Prediction] = None,
                      int8: Optional[Prediction] = None,
-                     mxfp4: Optional[Prediction] = None) -> None:
+                     mxfp4: Optional[Prediction] = None,
+                     sparse24: Optional[Prediction] = None) -> None:
     """Write ``path`` (a NumPy .npz with log_probs, pred, labels, confusion) atomically:
     temporary file in the same directory, then ``os.replace``, as checkpoints are.  With
     ``adversarial`` (the prediction on the attacked images, ``--attack-eps``) the file also
     holds adv_log_probs, adv_pred and adv_confusion; with ``int8`` (the prediction under the
     int8 weight set, ``--quantize int8``) int8_log_probs, int8_pred and int8_confusion; with
-    ``mxfp4`` (``--quantize mxfp4``) mxfp4_log_probs, mxfp4_pred and mxfp4_confusion."""
+    ``mxfp4`` (``--quantize mxfp4``) mxfp4_log_probs, mxfp4_pred and mxfp4_confusion; with
+    ``sparse24`` (``--quantize sparse24``) sparse24_log_probs, sparse24_pred and
+    sparse24_confusion."""
     import os
     import tempfile
     more = {}
-    for prefix, p in (("adv", adversarial), ("int8", int8), ("mxfp4", mxfp4)):
+    for prefix, p in (("adv", adversarial), ("int8", int8), ("mxfp4", mxfp4),
+                      ("sparse24", sparse24)):
         if p is not None:
             more.update({prefix + "_log_probs": p.log_probs.numpy(), prefix + "_pred": p.pred.numpy(),
                          prefix + "_confusion": p.confusion.numpy()})

@@ -111,15 +111,15 @@ def _prediction(logits, labels):
 
 
 def check_quantize(model: str, quantize):
-    """`quantize` as None, "int8" or "mxfp4"; anything else, or a model other than the two MLPs
-    (whose fc1 takes the raw image bytes: csrc/kernels/mlp_i8.hip, mlp_mx4.hip), is a
-    ValueError."""
+    """`quantize` as None, "int8", "mxfp4" or "sparse24"; anything else, or a model other than the
+    two MLPs (whose fc1 takes the raw image bytes: csrc/kernels/mlp_i8.hip, mlp_mx4.hip,
+    mlp_sp24.hip), is a ValueError."""
     if quantize is None:
         return None
-    if quantize == "mxfp4":
+    if quantize in ("mxfp4", "sparse24"):
         if model not in ("mlp", "mlp2"):
-            raise ValueError(f"no mxfp4 kernel for quantize='mxfp4' on the {model} model: "
-                             "quantize=\"mxfp4\" is built for --arch mlp and mlp2 only")
+            raise ValueError(f"no {quantize} kernel for quantize='{quantize}' on the {model} model: "
+                             f"quantize=\"{quantize}\" is built for --arch mlp and mlp2 only")
         return quantize
     if quantize != "int8" or model not in ("mlp", "mlp2"):
         raise ValueError(f"no int8 kernel for quantize={quantize!r} on the {model} model: "
@@ -212,6 +212,49 @@ def predict_step_cpu_mxfp4(model: str, arena, q: dict, images_u8, labels=None):
     with I = sum_k wq u8 computed in float64 and rounded once to float32, then the reference
     forward's remaining layers in fp32."""
     acc = images_u8.reshape(-1, 784).to(torch.float64) @ torch.from_numpy(q["wq"]).to(torch.float64).t()
+    pre = torch.from_numpy(np.asarray(I8_ALPHA)) * acc.to(torch.float32) + torch.from_numpy(q["d1"])
+    return _prediction(_behind_fc1(model, arena, pre), labels)
+
+
+def prune_fc1_24(arena) -> dict:
+    """2:4 magnitude pruning of `arena`'s fc1 (docs/kernels.md "2:4 sparse evaluation"; the CPU twin
+    and oracle of mlp_prune_24).  A row is 196 groups of 4 consecutive columns; a group keeps the
+    two entries that rank first by (|w| descending, column ascending) with their fp32 bits (an
+    all-zero group: columns 0 and 1), the others become zero.  Weights are finite: NaN and Inf
+    are out of scope.  {"wp": float32 [128, 784] the dense pruned weights; "hi", "lo": int16 [128,
+    416] the bf16 bits of the survivors in column order, hi = bf16(w), lo = bf16(w - hi), rows
+    zero-padded from 392 on; "index": int32 [128, 28], word 4 kp + g holding the nibbles p0 |
+    p1 << 2 (the survivors' positions, p0 < p1) of groups 32 kp + 16 h + 4 g + q at bits 16 h +
+    4 q, zero for groups >= 196; "d1": float32 [128] = b1 - beta sum_k wp (the sum in float64,
+    rounded once; the kernel's fixed-order fp32 sum is within its bound of it)}, NumPy."""
+    w = arena.param("fc1.weight").detach().cpu().numpy().astype(np.float32).reshape(128, 196, 4)
+    b = arena.param("fc1.bias").detach().cpu().numpy().astype(np.float32)
+    a = np.abs(w)
+    i, j = np.arange(4)[:, None], np.arange(4)[None, :]
+    # entry j survives if fewer than two entries i rank before it
+    first = (a[..., :, None] > a[..., None, :]) | ((a[..., :, None] == a[..., None, :]) & (i < j))
+    keep = first.sum(axis=2) < 2
+    p0, p1 = keep.argmax(axis=2), 3 - keep[..., ::-1].argmax(axis=2)
+    nib = np.zeros((128, 7, 2, 4, 4), np.int64)                      # [n][kp][h][g][q]
+    nib.reshape(128, 224)[:, :196] = p0 | (p1 << 2)
+    shift = (16 * np.arange(2)[:, None, None] + 4 * np.arange(4)[None, None, :])
+    index = (nib << shift).sum(axis=(2, 4)).astype(np.uint32).view(np.int32).reshape(128, 28)
+    kept = torch.zeros(128, 416)
+    kept[:, :392] = torch.from_numpy(np.take_along_axis(w, np.stack([p0, p1], axis=2), axis=2).reshape(128, 392))
+    hi = kept.to(torch.bfloat16)
+    lo = (kept - hi.float()).to(torch.bfloat16)
+    wp = np.where(keep, w, np.float32(0)).reshape(128, 784)
+    t = MX4_BETA * wp.sum(axis=1, dtype=np.float64).astype(np.float32)
+    return {"wp": wp, "hi": hi.view(torch.int16).numpy(), "lo": lo.view(torch.int16).numpy(),
+            "index": index, "d1": (b - t).astype(np.float32)}
+
+
+@torch.no_grad()
+def predict_step_cpu_sparse24(model: str, arena, q: dict, images_u8, labels=None):
+    """predict_step_cpu with fc1 pruned 2:4 (`q`: prune_fc1_24 of `arena`): pre = alpha I + d1 with
+    I = sum_k wp u8 computed in float64 and rounded once to float32, then the reference forward's
+    remaining layers in fp32."""
+    acc = images_u8.reshape(-1, 784).to(torch.float64) @ torch.from_numpy(q["wp"]).to(torch.float64).t()
     pre = torch.from_numpy(np.asarray(I8_ALPHA)) * acc.to(torch.float32) + torch.from_numpy(q["d1"])
     return _prediction(_behind_fc1(model, arena, pre), labels)
 

@@ -73,7 +73,8 @@ class Mlp2Step(MlpStep):
 
     def _eval_forward(self, images, labels, b, ws):
         P, w1 = (self.P, self.w1split) if ws is None else ws
-        # (a quantised weight set: mlp_fwd_i8's or mlp_fwd_mx4's partials, and d1 in fc1.bias's place)
+        # (a quantised or pruned weight set: mlp_fwd_i8's, mlp_fwd_mx4's or mlp_fwd_sp24's partials,
+        # and d1 in fc1.bias's place)
         part, s = self._eval_fc1(images, labels, b, w1)
         self.C.mlp_hid_fwd(part, s, b, P["fc1.bias"], P["fc2.weight"], None, self.pre2,
                            ngroups=hid_groups(b))

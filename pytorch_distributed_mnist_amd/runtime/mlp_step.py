@@ -14,7 +14,9 @@ _eval_forward below -- mlp_fwd -- then cnn_head or cnn_predict_head.  With an in
 (weight_set_int8: predict(quantize="int8")) the chunk's fc1 is mlp_fwd_i8 on the integer MFMA
 instead (``csrc/kernels/mlp_i8.hip``, docs/kernels.md "int8 evaluation"), with an MXFP4 one
 (weight_set_mxfp4: predict(quantize="mxfp4")) mlp_fwd_mx4 on the block-scaled MFMA
-(``csrc/kernels/mlp_mx4.hip``, docs/kernels.md "MXFP4 evaluation"); the head is the same.
+(``csrc/kernels/mlp_mx4.hip``, docs/kernels.md "MXFP4 evaluation"), with a 2:4-pruned one
+(weight_set_sparse24: predict(quantize="sparse24")) mlp_fwd_sp24 on the structured-sparsity MFMA
+(``csrc/kernels/mlp_sp24.hip``, docs/kernels.md "2:4 sparse evaluation"); the head is the same.
 """
 from __future__ import annotations
 
@@ -73,6 +75,24 @@ class Mx4Fc1(NamedTuple):
     byte per 32 columns), and the partials buffer mlp_fwd_mx4 writes (sized as Int8Fc1's)."""
     codes: torch.Tensor
     scales: torch.Tensor
+    part: torch.Tensor
+
+
+def mlp_sp24_splitk(b: int) -> int:
+    """Split-K of mlp_fwd_sp24 for b rows: mlp_i8_splitk's rule, the 13 k-steps of 64 dense
+    columns over 13 workgroups per 16-row m-tile while the launch stays within 512 workgroups (b
+    <= 624), else 1."""
+    return 13 if -(-b // 16) * 13 <= 512 else 1
+
+
+class Sp24Fc1(NamedTuple):
+    """fc1 of a 2:4-pruned weight set, in the place of the hi / lo planes: whi / wlo bf16 [128 x
+    416] (the two survivors of every 4 columns, hi = bf16(w), lo = bf16(w - hi), rows zero-padded
+    to 832 dense columns), index int32 [128 x 28] (their 2-bit positions, a word per two k-steps
+    of a lane group), and the partials buffer mlp_fwd_sp24 writes (sized as Int8Fc1's)."""
+    whi: torch.Tensor
+    wlo: torch.Tensor
+    index: torch.Tensor
     part: torch.Tensor
 
 
@@ -146,6 +166,23 @@ class MlpStep(GpuStepBase):
         return P, Mx4Fc1(codes, scales,
                          torch.empty(MX4_PART_ROWS * 128, dtype=torch.float32, device=dev))
 
+    @torch.no_grad()
+    def weight_set_sparse24(self, arena):
+        """The 2:4-pruned weight set of `arena`, built by one mlp_prune_24 launch: (name views
+        with fc1.bias replaced by d1, Sp24Fc1).  As weight_set_int8: fresh tensors, outside any
+        capture, nothing of `arena` or of the training step is touched."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("weight_set_sparse24() allocates: call it outside a graph capture")
+        dev, half = self.device, self.C.MLP_SP24_KPAD // 2
+        whi, wlo = (torch.empty(128 * half, dtype=torch.bfloat16, device=dev) for _ in range(2))
+        index = torch.empty(128 * 28, dtype=torch.int32, device=dev)
+        d1 = torch.empty(128, dtype=torch.float32, device=dev)
+        self.C.mlp_prune_24(arena.param("fc1.weight"), arena.param("fc1.bias"), whi, wlo, index, d1)
+        P = {n: arena.param(n) for n in self.names}
+        P["fc1.bias"] = d1
+        return P, Sp24Fc1(whi, wlo, index,
+                          torch.empty(I8_PART_ROWS * 128, dtype=torch.float32, device=dev))
+
     def optimizer_segments(self):
         segs = []
         for p in self.arena.spec.params:
@@ -183,7 +220,12 @@ class MlpStep(GpuStepBase):
 
     def _eval_fc1(self, images, labels, b, w1):
         """fc1's partials and ylab of b <= EVAL_CHUNK rows for evaluation: (part, splitk); w1 is
-        the hi / lo planes, or the Int8Fc1 / Mx4Fc1 of a quantised weight set."""
+        the hi / lo planes, or the Int8Fc1 / Mx4Fc1 / Sp24Fc1 of a quantised or pruned weight
+        set."""
+        if isinstance(w1, Sp24Fc1):
+            s = mlp_sp24_splitk(b)
+            self.C.mlp_fwd_sp24(images, labels, b, w1.whi, w1.wlo, w1.index, w1.part, self.ylab, s)
+            return w1.part, s
         if isinstance(w1, Mx4Fc1):
             s = mlp_mx4_splitk(b)
             self.C.mlp_fwd_mx4(images, labels, b, w1.codes, w1.scales, w1.part, self.ylab, s)

@@ -31,7 +31,8 @@ from ..optim.schedule import ScheduleSpec
 from ..utils.metrics import DeviceMetrics
 from .cpu_step import (attack_step_cpu, check_attack, check_quantize, eval_step_cpu,
                        predict_step_cpu, predict_step_cpu_int8, predict_step_cpu_mxfp4,
-                       quantize_fc1, quantize_fc1_mxfp4, train_step_cpu, tta_reduce_cpu)
+                       predict_step_cpu_sparse24, prune_fc1_24, quantize_fc1, quantize_fc1_mxfp4,
+                       train_step_cpu, tta_reduce_cpu)
 from .structure import StepStructure
 
 
@@ -62,8 +63,8 @@ class TrainProgram:
                  quantize: Optional[str] = None):
         self.model = model
         # predict()'s default for its `quantize` keyword (load_predictor(quantize="int8")): None,
-        # "int8" or "mxfp4", the MLPs' first layer on int8 or MXFP4 weights.  evaluate() and
-        # training never quantise.
+        # "int8", "mxfp4" or "sparse24", the MLPs' first layer on int8, MXFP4 or 2:4-pruned
+        # weights.  evaluate() and training never quantise or prune.
         self.quantize = check_quantize(model, quantize)
         # test-time augmentation (--tta V): evaluate() and predict() classify every image
         # together with V - 1 distorted views of it and combine the V log-softmax rows into the
@@ -387,8 +388,11 @@ class TrainProgram:
         integer matrix cores, everything behind it as it is (docs/kernels.md "int8 evaluation");
         or "mxfp4" -- that layer with OCP MXFP4 weights (E2M1 codes, a power-of-two scale per 32
         weights) and the exact pixels on the block-scaled MFMA (docs/kernels.md "MXFP4
-        evaluation"); the weights quantised are the ones ``average`` picks.  Not combined with
-        test-time views; another value or model raises ValueError."""
+        evaluation"); or "sparse24" -- that layer with 2 of every 4 consecutive weights of a row
+        kept (the larger magnitudes) at fp32 precision and the exact pixels on the
+        structured-sparsity MFMA (docs/kernels.md "2:4 sparse evaluation"); the weights quantised
+        or pruned are the ones ``average`` picks.  Not combined with test-time views; another
+        value or model raises ValueError."""
         arena = self._eval_arena(average)
         views = self.tta if tta is None else check_tta(tta, self.tta_augment)
         quantize = check_quantize(self.model, self.quantize if quantize is None else quantize)
@@ -408,6 +412,8 @@ class TrainProgram:
         if self.gpu is not None:
             if quantize == "mxfp4":
                 ws = self.gpu.weight_set_mxfp4(arena)
+            elif quantize == "sparse24":
+                ws = self.gpu.weight_set_sparse24(arena)
             elif quantize is not None:
                 ws = self.gpu.weight_set_int8(arena)
             else:
@@ -425,8 +431,10 @@ class TrainProgram:
             return Prediction(*self._predict_tta_cpu(arena, images, labels, views))
         step = predict_step_cpu
         if quantize is not None:
-            q, qstep = ((quantize_fc1_mxfp4(arena), predict_step_cpu_mxfp4) if quantize == "mxfp4"
-                        else (quantize_fc1(arena), predict_step_cpu_int8))
+            prepare, qstep = {"mxfp4": (quantize_fc1_mxfp4, predict_step_cpu_mxfp4),
+                              "sparse24": (prune_fc1_24, predict_step_cpu_sparse24),
+                              "int8": (quantize_fc1, predict_step_cpu_int8)}[quantize]
+            q = prepare(arena)
             step = lambda m, a, x, y: qstep(m, a, q, x, y)   # noqa: E731
         outs = [step(self.model, arena, images[start:start + size],
                      None if labels is None else labels[start:start + size])

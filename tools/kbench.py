@@ -4,7 +4,8 @@ two-hidden-layer MLP's hidden kernels (mlp_hid_fwd at both workgroup splits) and
 `kbench.py mlp_attack [B ...]`: mlp_attack at both workgroup splits beside its mlp_fwd;
 `kbench.py mlp_i8 [B ...]`: mlp_fwd_i8 at both splits beside mlp_fwd, and mlp_quant_w1;
 `kbench.py mlp_mx4 [B ...]`: mlp_fwd_mx4 at both splits beside mlp_fwd_i8 and mlp_fwd, and
-mlp_quant_mx4."""
+mlp_quant_mx4; `kbench.py mlp_sp24 [B ...]`: mlp_fwd_sp24 at both splits beside those three, and
+mlp_prune_24."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -171,7 +172,41 @@ def mlp_mx4(sizes):
               " ".join(f"{a:.2f}|{b:.2f}|{c:.2f}|{d:.2f}" for a, b, c, d in t), flush=True)
 
 
+def mlp_sp24(sizes):
+    """mlp_fwd_sp24 at both splits beside mlp_fwd, mlp_fwd_i8 and mlp_fwd_mx4 (each at its own
+    rule's split) on the same rows, interleaved, at each batch size, and the one-off mlp_prune_24
+    (csrc/kernels/mlp_sp24.hip)."""
+    from pytorch_distributed_mnist_amd.runtime.mlp_step import (mlp_i8_splitk, mlp_mx4_splitk,
+                                                                mlp_sp24_splitk)
+    p = build_local_program("mlp", "fp32", "cuda", 1, train, test, optimizer="sgd", lr=0.01,
+                            use_graphs=False)
+    st = p.gpu
+    (_, w8), (_, w4), (_, ws) = (f(p.arena) for f in (st.weight_set_int8, st.weight_set_mxfp4,
+                                                      st.weight_set_sparse24))
+    whi, wlo, index, d1 = (torch.empty_like(t) for t in (ws.whi, ws.wlo, ws.index, w8.c1))
+    pk = lambda: st.C.mlp_prune_24(p.arena.param("fc1.weight"), p.arena.param("fc1.bias"), whi, wlo,
+                                   index, d1)
+    print("mlp_prune_24 x3: " + " ".join(f"{timeit(pk):.2f}" for _ in range(3)), flush=True)
+    n = 128 * 784
+    for B in sizes:
+        x = train.images[:B].cuda()
+        y = train.labels[:B].to(torch.int32).cuda()
+        part = torch.empty(25 * B * 128, device="cuda")
+        S, S8, S4 = mlp_splitk(B), mlp_i8_splitk(B), mlp_mx4_splitk(B)
+        f32 = lambda: st.C.mlp_fwd(x, y, None, B, B, st.w1split[:n], st.w1split[n:], part, st.ylab, S)
+        i8 = lambda: st.C.mlp_fwd_i8(x, y, B, w8.q1, w8.c1, part, st.ylab, S8)
+        mx = lambda: st.C.mlp_fwd_mx4(x, y, B, w4.codes, w4.scales, part, st.ylab, S4)
+        sp = lambda s: st.C.mlp_fwd_sp24(x, y, B, ws.whi, ws.wlo, ws.index, part, st.ylab, s)
+        t = [(timeit(f32), timeit(i8), timeit(mx), timeit(lambda: sp(13)), timeit(lambda: sp(1)))
+             for _ in range(3)]
+        print(f"mlp_sp24 B={B:5d} mlp_fwd S={S}|mlp_fwd_i8 S={S8}|mlp_fwd_mx4 S={S4}|mlp_fwd_sp24 "
+              f"S=13|S=1 (rule: {mlp_sp24_splitk(B)}) x3: " +
+              " ".join("|".join(f"{v:.2f}" for v in r) for r in t), flush=True)
+
+
 def main():
+  if sys.argv[1:2] == ["mlp_sp24"]:
+      return mlp_sp24([int(b) for b in (sys.argv[2:] or ["32", "256", "624", "625", "2048"])])
   if sys.argv[1:2] == ["mlp_mx4"]:
       return mlp_mx4([int(b) for b in (sys.argv[2:] or ["32", "256", "1168", "1169", "2048"])])
   if sys.argv[1:2] == ["mlp_i8"]:
